@@ -30,6 +30,8 @@ Extra objects on the JSON line:
                 Fused launch: 4*[2*B*P*H*W + 4*B*51*H*W + B*H*W] with P = planes per frame handed over
                 (1: 6,945,767,424 B at B=8 1024x1024; 3: 7,079,985,152 B; SURVEY 8d counts 866.4 B per restored pixel
                 for the unfused pair); unfused call: 4*[B*3*(H+50)(W+50) + 2*B*51*H*W + B*3*H*W] = 3,633,949,056 B.
+                `traffic` is measured by two rocprofv3 --pmc child passes with --full, else read from --traffic-json.
+A plain run stops there: set-up, warm-up, the K timed steps, --dump-outputs, the line.  With --full it goes on to:
   cpu_baseline  the CPU oracle (OpenMP build of oracle/sepconv_oracle.c, kind "port") timed on this box's host cores
                 on a bounded sample of the same workload; its first tile also goes through the TIMED GPU step (as image 0
                 of a full batch, so the same kernel instance runs) and is compared: the "PSNR vs ref" half of the metric.
@@ -38,8 +40,12 @@ Extra objects on the JSON line:
                 fp32 matrix peak); the SFF fusion TRAINING step of BASELINE config 3 (global batch 16 at 256x256
                 STRONG-scaled over the ranks: frozen flow net -> warp -> UNet -> L1 -> backward -> one flat RCCL
                 all-reduce -> Adam), with the all-reduce time and bucket size.
+  metric_as_worded  the SFF restoration forward at the headline size, with its own CPU baseline.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--size 1024] [--batch 8]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--size 1024] [--batch 8] [--full] [--dump-outputs DIR]
+       --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned as DIR/output.npy (float32;
+       above 60 MB a fixed, seeded sample of its elements); the inputs are seeded, so runs with the same arguments compare
+       output for output.
        N > 1 without WORLD_SIZE in the environment: this process only spawns `python -m torch.distributed.run` with N
        ranks (before it touches a GPU) and returns its exit code; under torch.distributed.run it is one rank of N.
 """
@@ -112,6 +118,9 @@ def parse():
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--algo", type=int, default=0, help="0 auto, 1 direct, 2 mfma")
+    ap.add_argument("--full", action="store_true", help="after the headline: the live PMC traffic passes, the CPU baselines, metric_as_worded "
+                    "and the `extra` entries (the --no-* options below switch single parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/output.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="no `extra` entries (profiling runs)")
     ap.add_argument("--no-metric-as-worded", action="store_true", help="skip the top-level metric_as_worded object (the SFF restoration forward + its CPU baseline)")
@@ -129,7 +138,10 @@ def parse():
                     help="PMC-derived HBM bytes per launch written by tools/pmc_traffic.py (the fallback when the live passes fail)")
     ap.add_argument("--no-live-traffic", action="store_true", help="do not run the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of the headline "
                     "launch as child processes before the timed run; roofline.traffic then comes from --traffic-json")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -415,6 +427,26 @@ def max_over_ranks(torch, dist, dt, device, backend):
     t = torch.tensor([dt], device=device if backend == "nccl" else "cpu", dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item())
+
+
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000
+
+
+def dump_outputs(torch, out_dir, arrays):
+    """--dump-outputs: each tensor as out_dir/<name>.npy in float32; one larger than DUMP_LIMIT_BYTES is written as the elements at a
+    fixed, seeded set of flat positions (the same positions for the same shape), so two builds compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        cap = DUMP_LIMIT_BYTES // 4
+        if flat.numel() > cap:
+            idx = np.unique(np.random.default_rng(20240601).integers(0, flat.numel(), size=cap))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            a = flat.float().cpu().numpy()
+        else:
+            a = flat.float().cpu().numpy().reshape(tuple(t.shape))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 LINE_LIMIT = 7800          # the driver keeps the last 8 KB of stdout: a longer line would lose its head and parse as nothing
@@ -847,8 +879,8 @@ def main():
         raise SystemExit("WORLD_SIZE=%d but --gpus %d" % (world, args.gpus))
 
     # HBM traffic of the headline launch from PMC counters, collected now: nothing in this process has touched the GPU yet
-    measured_traffic = (None, "live passes switched off")
-    if world == 1 and not args.no_live_traffic:
+    measured_traffic = (None, "live passes switched off" if args.full else "live passes run with --full only")
+    if world == 1 and args.full and not args.no_live_traffic:
         if any(k.startswith(("ROCP_", "ROCPROF")) for k in os.environ):
             measured_traffic = (None, "this run is itself under a profiler")         # no profiler inside a profiler
         else:
@@ -888,14 +920,23 @@ def main():
     wl = ApplyWorkload(args, B, S, device, rank)
     n_ev = wl.launches_per_step * args.steps
     ev = ([torch.cuda.Event(enable_timing=True) for _ in range(n_ev)], [torch.cuda.Event(enable_timing=True) for _ in range(n_ev)])
+    last = {}
+
+    def timed_step(k):
+        out = wl.step(ev, k)
+        if k == args.steps - 1:
+            last["output"] = out                       # what the caller of the timed path receives in the last step
 
     with torch.no_grad():
         # Untimed pre-warm, before the W warm-up steps of the contract: an MI355X that has been idle needs a few hundred ms under load
         # to reach the clocks it then holds (measured: the same 20 timed steps 2.5 % slower with 5 warm-up steps = 7 ms than with
         # 500; steps of other benchmarks timed within 100 ms of idle ran 30-50 % slow).  Nothing of it is timed.
-        dt = timed(torch, dist, wl.step, lambda k: wl.step(ev, k), args.steps, args.warmup, args.prewarm_s)
+        dt = timed(torch, dist, wl.step, timed_step, args.steps, args.warmup, args.prewarm_s)
     dt = max_over_ranks(torch, dist, dt, device, backend)
     kern_ms = sum(a.elapsed_time(b) for a, b in zip(*ev)) / n_ev
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, last)
+    del last
 
     line = None
     if rank == 0:
@@ -952,12 +993,12 @@ def main():
                          "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
                          "bytes_per_launch": alg_bytes, "launch_ms": round(kern_ms, 4)},
         }
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(S, args.rgb, wl.apply_first_of_batch)
     del wl, ev
     torch.cuda.empty_cache()
 
-    if not args.no_metric_as_worded:
+    if args.full and not args.no_metric_as_worded:
         # every rank runs the step (independent tiles, weak scaling); rank 0 reports
         try:
             maw = metric_as_worded(args, torch, dist, device, backend, rank, world, with_cpu=(world == 1 and not args.no_cpu_baseline))
@@ -967,7 +1008,7 @@ def main():
         if rank == 0:
             line["metric_as_worded"] = maw
 
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         which = set((args.extra_only or EXTRAS).split(","))
         # the headline line must come out even if an extra entry hangs (a collective that one rank never reaches, a capture that never
         # returns): after --extra-timeout seconds every rank leaves, rank 0 printing the line with what it has
