@@ -58,6 +58,9 @@
 #ifndef SSTEM_COEF_AUX
 #define SSTEM_COEF_AUX 0   // cache-policy bits of the coefficient loads of the trusted-gray kernel (gfx950: 1 sc0, 2 nt, 16 sc1)
 #endif
+#ifndef SSTEM_PAIR_COEF_AUX
+#define SSTEM_PAIR_COEF_AUX 2 // the same bits for the row-pair fused apply (blocked coefficients only): nt, -3.8 % at C2 (profiles/r06)
+#endif
 
 namespace sstem {
 
@@ -696,23 +699,24 @@ __device__ __forceinline__ rsrc_t coef_rsrc(const float* image_planes, uint32_t 
 {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(image_planes), 0, (int)bytes, 0x00020000);
 }
+template <int AUX = SSTEM_COEF_AUX>
 __device__ __forceinline__ float bld(rsrc_t r, uint32_t voff, uint32_t soff)
 {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, SSTEM_COEF_AUX));
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, AUX));
 }
 // bf16 coefficient tensors (round 5: the ..._bf16coef entry points of include/sstem_sepconv.h -- BASELINE config 5, "bf16 activations
 // with fp32 sepconv accumulate"; SURVEY 8(b), 8(d): the two 51 H W terms of the byte model halved).  The kernels keep ALL their
 // offset arithmetic in fp32 bytes; a bf16 tensor's element sits at half that offset, is requested as 16 bits and widened to fp32 by
 // one shift (bf16 IS the upper half of an fp32): the same products, the same fp32 sums as on an fp32 tensor that holds the rounded
 // values.
-template <bool BF>
+template <bool BF, int AUX = SSTEM_COEF_AUX>
 __device__ __forceinline__ float bldc(rsrc_t r, uint32_t voff, uint32_t soff)
 {
     if constexpr (BF) {
-        const uint32_t v = (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(r, (int)(voff >> 1), (int)(soff >> 1), SSTEM_COEF_AUX);
+        const uint32_t v = (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(r, (int)(voff >> 1), (int)(soff >> 1), AUX);
         return __builtin_bit_cast(float, v << 16);
     } else {
-        return bld(r, voff, soff);
+        return bld<AUX>(r, voff, soff);
     }
 }
 // resource over one image's coefficients: `tensor` + elem_off ELEMENTS (fp32 or bf16), fp32_bytes = the image's size as an fp32 tensor
@@ -733,7 +737,7 @@ __device__ __forceinline__ void pin_s(uint32_t& v) { asm volatile("" : "+s"(v));
 // four planes = eight lines per instruction, every segment asked for by four consecutive instructions) costs the
 // coefficient stream 6-12 % of its rate -- the per-CU L1 has to merge those requests; bypassing it (nt / sc1)
 // costs 25-30 %.  So the skew is applied in registers instead (skew_taps_in_place).
-template <bool BF = false>
+template <bool BF = false, int AUX = SSTEM_COEF_AUX>
 __device__ __forceinline__ void load_taps_buf(float (&dst)[KSTEPS], rsrc_t r, uint32_t rowoff, uint32_t pstride,
                                               uint32_t xoff, const int t0 = 0, const int t1 = F)
 {
@@ -745,7 +749,7 @@ __device__ __forceinline__ void load_taps_buf(float (&dst)[KSTEPS], rsrc_t r, ui
 #if SSTEM_ABLATE & 1
         dst[f] = 0.25f; continue;
 #endif
-        dst[f] = bldc<BF>(r, xoff, soff);
+        dst[f] = bldc<BF, AUX>(r, xoff, soff);
         soff += pstride;
         pin_s(soff);
     }
@@ -757,6 +761,7 @@ __device__ __forceinline__ void load_taps_buf(float (&dst)[KSTEPS], rsrc_t r, ui
 // for the three entries at either end, whose out-of-range lanes read a valid tap and are zeroed.  t in [t0, t1) (constants after
 // unrolling).  Same values as load_taps_buf + skew_taps_in_place: bit-identical results, ~150 VALU instructions per pixel row less
 // (vector instructions do not co-issue with the 4x4x1 MFMA).
+template <int AUX = SSTEM_COEF_AUX>
 __device__ __forceinline__ void load_taps_skewed_buf(float (&dst)[KSTEPS], rsrc_t r, uint32_t rowoff, uint32_t pstride,
                                                      uint32_t xoff, int sub, const int t0 = 0, const int t1 = KSTEPS)
 {
@@ -770,14 +775,14 @@ __device__ __forceinline__ void load_taps_skewed_buf(float (&dst)[KSTEPS], rsrc_
         dst[t] = 0.25f; continue;
 #endif
         if (t >= 3 && t < F) {
-            dst[t] = bld(r, vo, soff);
+            dst[t] = bld<AUX>(r, vo, soff);
             soff += pstride;
             pin_s(soff);
         } else {
             int f = t - sub;
             const bool ok = f >= 0 && f < F;
             f = f < 0 ? 0 : (f > F - 1 ? F - 1 : f);
-            const float v = bld(r, xoff + (uint32_t)f * pstride, rowoff);
+            const float v = bld<AUX>(r, xoff + (uint32_t)f * pstride, rowoff);
             dst[t] = ok ? v : 0.f;
         }
     }
@@ -1116,6 +1121,233 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma(
             float dummy[1];
 #pragma unroll 1
             for (int rr = 0; rr < nrows; ++rr) do_row(hs, dummy, rr, rr + 1 < nrows);
+        }
+    }
+}
+
+// fn(std::integral_constant<int, I>{}) for I = I0 .. N-1: a loop whose counter is a constant expression in the body
+template <int I, int N, typename Fn>
+__device__ __forceinline__ void static_for(Fn&& fn)
+{
+    if constexpr (I < N) {
+        fn(std::integral_constant<int, I>{});
+        static_for<I + 1, N>(fn);
+    }
+}
+
+// ---- trusted-gray fused apply, row pairs (blocked coefficients) ---------------------------------------------------------------
+// sepconv_gray_mfma<2, 4, RPW, *, false, 2, true> with a wave's rows taken two at a time, y and y + 4.  The A operand of 4-row tile T
+// of row y + 4 (tile rows y + 4 + 4 T + i) is the A operand of tile T + 1 of row y, so one ds_read_b128 of "A tile" a = 0..13 feeds
+// two MFMAs: row y's tile a (a <= 12, B operand hA) and row y + 4's tile a - 1 (a >= 1, B operand hB).  Per k-chunk and pair: 14 LDS
+// reads instead of 26, four independent accumulator chains instead of two.  Every tile's chain still runs t = 0..53 on the same A and
+// B values and every output still sums V[fy] * T[fy] over fy ascending: the same bits as the one-row kernel.
+//   * groups k = 0..6 take A tiles 2k, 2k + 1 (13 = rows 52..55 of row y: the tile's last staged row is the pad row of the wave's
+//     last y + 4, TR + 50);
+//   * B operands of both rows stay resident (108 VGPRs); their refills for the next pair stream in during group 6, chunk by chunk, as
+//     soon as the entries are consumed;
+//   * vertical taps: the taps group k combines are requested at the start of group k - 2 (groups 0 and 1: groups 5 and 6 of the
+//     previous pair), not a whole row ahead -- two rows' worth would not fit beside the two B operands;
+//   * 240 VGPRs (16 below the 2-waves-per-SIMD bound), no spills: 2 waves per SIMD.  A pair whose second row lies below the image (odd row count of a bottom tile) computes it on
+//     clamped coefficient rows and does not store it.
+template <int WAVES, int RPW, int WPE>
+__global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma_pair(
+    const float* __restrict__ in_a, const float* __restrict__ ver_a, const float* __restrict__ hor_a,
+    float* __restrict__ out, TileArgs args, FusedArgs fa)
+{
+    static_assert(WAVES == 4, "the rows of a pair are one 4-row MFMA tile apart");
+    static_assert(RPW % 2 == 0, "row pairs");
+    if (fa.gray_flag && *fa.gray_flag == 0) return;   // not identical: the generic build owns this call
+    constexpr int TR = WAVES * RPW;
+    constexpr int ROWS = TR + F;          // +50 halo +1 pad row
+    constexpr int RS = rm_pitch(1);
+    constexpr int YSTEP = WAVES;
+    constexpr int NA = 2;                 // A tiles per group
+    constexpr int NGRP = 7;               // groups per pair
+    constexpr int LV = 2;                 // vertical taps requested LV groups ahead
+    constexpr uint32_t TAP = 256u;        // bytes between consecutive taps of one row segment
+    // cache policy of the coefficient loads: in the blocked layout every 128-B line is read by exactly one instruction, so nothing is
+    // lost by not keeping it (unlike NCHW taps, where nt cost the stream 25-30 %, profiles/r01/q_ablation_gray_stream.txt)
+    constexpr int AUX = SSTEM_PAIR_COEF_AUX;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+
+    int64_t b, ty, tx;
+    decode_block(args, b, ty, tx);
+    const int64_t H = args.H, W = args.W;
+    const int64_t plane = H * W;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t y0 = ty * TR, x0 = tx * 64;
+
+    const int lane = threadIdx.x & 63;
+    const int blk = lane >> 2, sub = lane & 3;
+    const bool xok = (x0 + lane) < W;
+    const uint32_t xoff = (uint32_t)(xok ? lane : 0) * 4u;
+    auto clampy = [&](int64_t y) __attribute__((always_inline)) -> int64_t { return y < H ? y : H - 1; };
+    const int64_t yfirst = clampy(y0 + wave);
+
+    const uint32_t seg_row = (uint32_t)args.tiles_x * (uint32_t)(F * 256);
+    const uint32_t img_bytes = (uint32_t)H * seg_row;
+    const int64_t img_elems = (int64_t)(img_bytes >> 2);
+    const uint32_t seg_x = (uint32_t)tx * (uint32_t)(F * 256);
+    auto rowoff = [&](int64_t y) __attribute__((always_inline)) -> uint32_t { return (uint32_t)clampy(y) * seg_row + seg_x; };
+
+    float hA[KSTEPS], hB[KSTEPS], vA[F], vB[F];
+
+    // taps fy in [f0, f1) of one row, offset ro: (tap 0, row, x0); tap stride ps (0: re-read one hot segment, results unused)
+    auto vload = [&](float (&v)[F], rsrc_t r, uint32_t ro, uint32_t ps, const int f0, const int f1) __attribute__((always_inline)) {
+        uint32_t soff = ro + (uint32_t)f0 * ps;
+        pin_s(soff);
+#pragma unroll
+        for (int f = 0; f < F; ++f) {
+            if (f < f0 || f >= f1) continue;
+            v[f] = bldc<false, AUX>(r, xoff, soff);
+            soff += ps;
+            pin_s(soff);
+        }
+    };
+    // the vertical taps group k combines: row y fy in [8k, 8k + 8), row y + 4 fy in [8k - 4, 8k + 4) (clipped to [0, 51))
+    auto vload_group = [&](const int k, rsrc_t r, uint32_t roA, uint32_t roB, uint32_t ps) __attribute__((always_inline)) {
+        vload(vA, r, roA, ps, 8 * k, (8 * k + 8 < F) ? 8 * k + 8 : F);
+        vload(vB, r, roB, ps, (8 * k - 4 > 0) ? 8 * k - 4 : 0, (8 * k + 4 < F) ? 8 * k + 4 : F);
+    };
+    auto hload = [&](float (&h)[KSTEPS], rsrc_t r, uint32_t ro, uint32_t ps, const int t0, const int t1) __attribute__((always_inline)) {
+        if constexpr (SSTEM_BLK_SKEWLD) load_taps_skewed_buf<AUX>(h, r, ro, ps, xoff, sub, t0, t1 < KSTEPS ? t1 : KSTEPS);
+        else load_taps_buf<false, AUX>(h, r, ro, ps, xoff, t0 < F ? t0 : F, t1 < F ? t1 : F);
+    };
+    {   // coefficients of my first pair (phase 0); the rest arrive through the refills below
+        const rsrc_t rv = coef_rsrc_c<false>(ver_a, b * img_elems, img_bytes);
+        const rsrc_t rh = coef_rsrc_c<false>(hor_a, b * img_elems, img_bytes);
+        const uint32_t oA = rowoff(yfirst), oB = rowoff(yfirst + YSTEP);
+#pragma unroll
+        for (int k = 0; k < LV; ++k) vload_group(k, rv, oA, oB, TAP);
+        hload(hA, rh, oA, TAP, 0, KSTEPS);
+        hload(hB, rh, oB, TAP, 0, KSTEPS);
+    }
+
+#pragma unroll 1
+    for (int ph = 0; ph < 2; ++ph) {
+        const float* in = ph ? fa.in2 : in_a;
+        const float* ver = ph ? fa.ver2 : ver_a;
+        const float* hor = ph ? fa.hor2 : hor_a;
+        const bool next_ph = ph == 0;
+        const rsrc_t rv_cur = coef_rsrc_c<false>(ver, b * img_elems, img_bytes);
+        const rsrc_t rh_cur = coef_rsrc_c<false>(hor, b * img_elems, img_bytes);
+        const rsrc_t rv_nxt = coef_rsrc_c<false>(next_ph ? fa.ver2 : ver, b * img_elems, img_bytes);
+        const rsrc_t rh_nxt = coef_rsrc_c<false>(next_ph ? fa.hor2 : hor, b * img_elems, img_bytes);
+
+        if (ph) __syncthreads();          // every wave is done reading the first image's tile
+#if SSTEM_GRAY_DMA
+        stage_gray_tile_dma<WAVES * 64, ROWS, RS, true>(lds, in + (b * args.in_planes) * plane, (int)H, (int)W, (int)y0, (int)x0);
+#else
+        stage_gray_tile<WAVES * 64, ROWS, RS, true>(lds, in + (b * args.in_planes) * plane, (int)H, (int)W, (int)y0, (int)x0);
+#endif
+        __syncthreads();
+
+        int nrows = 0;                      // rows of this tile that are mine (wave-uniform)
+        if (y0 + wave < H) {
+            const int64_t left = (H - 1 - (y0 + wave)) / YSTEP + 1;
+            nrows = left < RPW ? (int)left : RPW;
+        }
+#pragma unroll 1
+        for (int rr = 0; rr < nrows; rr += 2) {
+            const bool more = rr + 2 < nrows;                            // is there a next pair in this phase?
+            const bool two = rr + 1 < nrows;                             // is the pair's second row inside the image?
+            const int yl = wave + rr * YSTEP;
+            const int64_t y = y0 + yl;
+            // where the refills go: my next pair, the second phase's first pair, or (last pair of the launch) one hot segment of my
+            // own row again (tap stride 0)
+            const int64_t ynext = more ? (y + 2 * YSTEP) : (next_ph ? yfirst : y);
+            const uint32_t pn = (more || next_ph) ? TAP : 0u;
+            const uint32_t curA = rowoff(y), curB = rowoff(y + YSTEP);
+            const uint32_t nxtA = rowoff(ynext), nxtB = rowoff(ynext + YSTEP);
+            const rsrc_t rv_n = more ? rv_cur : rv_nxt;
+            const rsrc_t rh_n = more ? rh_cur : rh_nxt;
+            float* dstA = out + (b * H + y) * W + x0;
+            float* dstB = out + (b * H + clampy(y + YSTEP)) * W + x0;
+            pin_uniform(dstA);
+            pin_uniform(dstB);
+            const float parkedA = *stg_ptr(dstA, xoff);                  // the first image's channel sums (second phase), requested
+            const float parkedB = *stg_ptr(dstB, xoff);                  // early: their waits do not drain the refills behind them
+
+            if constexpr (!SSTEM_BLK_SKEWLD) {                           // the raw taps requested during the last pair (waits here)
+                skew_taps_in_place(hA, sub);
+                skew_taps_in_place(hB, sub);
+            }
+            const float* arow = lds + (yl + sub) * RS + blk * 4;
+            f32x4 ar[2][NA];
+#pragma unroll
+            for (int c = 0; c < NA; ++c) ar[0][c] = *reinterpret_cast<const f32x4*>(arow + c * 4 * RS);
+            float oA = 0.f, oB = 0.f;
+            static_for<0, NGRP>([&](auto kc) __attribute__((always_inline)) {
+                constexpr int k = decltype(kc)::value;
+                if (k + LV < NGRP) vload_group(k + LV, rv_cur, curA, curB, TAP);
+                else vload_group(k + LV - NGRP, rv_n, nxtA, nxtB, pn);
+                // chain (row y, A tile 2k + c) exists for 2k + c <= 12, chain (row y + 4, A tile 2k + c) for 2k + c >= 1
+                f32x4 accA[NA], accB[NA];
+#pragma unroll
+                for (int c = 0; c < NA; ++c) { accA[c] = (f32x4){0.f, 0.f, 0.f, 0.f}; accB[c] = accA[c]; }
+                const float* abase = arow + k * (NA * 4) * RS;
+                const float* anext = arow + (k + 1) * (NA * 4) * RS;
+#pragma unroll
+                for (int tq = 0; tq < 14; ++tq) {
+                    const int cc = k * 14 + tq;                          // running chunk number: ring slot cc % 2
+                    if (tq + 1 < 14) {
+#pragma unroll
+                        for (int c = 0; c < NA; ++c)
+                            ar[(cc + 1) % 2][c] = *reinterpret_cast<const f32x4*>(abase + c * 4 * RS + (tq + 1) * 4);
+                    } else if (k + 1 < NGRP) {
+#pragma unroll
+                        for (int c = 0; c < NA; ++c)
+                            ar[(cc + 1) % 2][c] = *reinterpret_cast<const f32x4*>(anext + c * 4 * RS);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int t = tq * 4 + e;
+                        if (t < KSTEPS) {
+#pragma unroll
+                            for (int c = 0; c < NA; ++c) {
+                                const int a = 2 * k + c;
+                                if (a <= 12) accA[c] = __builtin_amdgcn_mfma_f32_4x4x1f32(ar[cc % 2][c][e], hA[t], accA[c], 0, 0, 0);
+                                if (a >= 1) accB[c] = __builtin_amdgcn_mfma_f32_4x4x1f32(ar[cc % 2][c][e], hB[t], accB[c], 0, 0, 0);
+                            }
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (k == NGRP - 1) {                                 // entries 4 tq .. 4 tq + 3 are done: the next pair's B operands
+                        hload(hA, rh_n, nxtA, pn, 4 * tq, 4 * tq + 4);
+                        hload(hB, rh_n, nxtB, pn, 4 * tq, 4 * tq + 4);
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < NA; ++c) {                           // fy ascending in both sums
+                    const int a = 2 * k + c;
+                    if (a <= 12)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if (4 * a + i < F) oA = fmaf(vA[4 * a + i], accA[c][i], oA);
+                }
+#pragma unroll
+                for (int c = 0; c < NA; ++c) {
+                    const int a = 2 * k + c;
+                    if (a >= 1)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if (4 * (a - 1) + i < F) oB = fmaf(vB[4 * (a - 1) + i], accB[c][i], oB);
+                }
+                asm volatile("" : "+v"(oA), "+v"(oB));   // here, not sunk to the stores: the accumulators and taps die now
+            });
+            if (xok) {   // channel sum, then the mean over channels of both images (model_interp.py:94-97)
+                const float csA = (oA + oA) + oA;
+                const float resA = ph ? (parkedA + csA) * (1.0f / 3) : csA;
+                *stg_ptr(dstA, xoff) = resA;
+                if (ph && fa.out_u8) fa.out_u8[(b * H + y) * W + x0 + lane] = numpy_u8_of(resA);
+                if (two) {
+                    const float csB = (oB + oB) + oB;
+                    const float resB = ph ? (parkedB + csB) * (1.0f / 3) : csB;
+                    *stg_ptr(dstB, xoff) = resB;
+                    if (ph && fa.out_u8) fa.out_u8[(b * H + y + YSTEP) * W + x0 + lane] = numpy_u8_of(resB);
+                }
+            }
         }
     }
 }
@@ -2755,11 +2987,42 @@ static hipError_t launch_gray_v(const float* in, const float* ver, const float* 
     return hipGetLastError();
 }
 
+// Row-pair form of the blocked fused apply (sepconv_gray_mfma_pair, 4 waves x 16 rows, 2 waves per SIMD).  Developer knob
+// SSTEM_GRAY_PAIR, read once, at the first trusted-gray launch of any kind: 0 = always the one-row kernel, 1 = the pair form when its
+// grid gives every CU at least two workgroups (default), 2 = always the pair form (A/B runs, tests).  At C2, same box: 1.319 ms against
+// 1.340 for the one-row kernel; a 4 x 8 pair form ran 1.340 -- two waves per SIMD need the taller tile's rows in flight, which a grid
+// of one workgroup per CU does not give (profiles/r06).
+static int gray_pair_variant()
+{
+    static const int v = [] { const char* e = getenv("SSTEM_GRAY_PAIR"); return e ? atoi(e) : 1; }();
+    return v;
+}
+
+template <int WAVES, int RPW, int WPE>
+static hipError_t launch_gray_pair_v(const float* in, const float* ver, const float* hor, float* out, TileArgs a,
+                                     hipStream_t s, const FusedArgs& fa)
+{
+    constexpr int TR = WAVES * RPW;
+    constexpr size_t lds_bytes = (size_t)(TR + F) * rm_pitch(1) * sizeof(float);
+    static_assert(lds_bytes * WPE <= 160 * 1024, "LDS");
+    auto k = sepconv_gray_mfma_pair<WAVES, RPW, WPE>;
+    static std::atomic<uint64_t> lds_set{0};
+    const hipError_t attr = set_lds(k, lds_bytes, lds_set);
+    if (attr != hipSuccess) return attr;
+    a.tiles_y = (a.H + TR - 1) / TR;
+    const int64_t nwg = a.B * a.tiles_y * a.tiles_x;
+    if (nwg <= 0 || nwg > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(WAVES * 64), lds_bytes, s, in, ver, hor, out, a, fa);
+    return hipGetLastError();
+}
+
 template <int MODE, bool BLK = false>
 static hipError_t launch_gray(const float* in, const float* vg, const float* hor, float* out, TileArgs a,
                               hipStream_t s, const FusedArgs& fa)
 {
     static const int forced = [] { const char* e = getenv("SSTEM_GRAY_SHAPE"); return e ? atoi(e) : -1; }();
+    const int pair = gray_pair_variant();
+    (void)pair;
     // default: the tall 2-waves-per-SIMD shape (fastest measured at C2) when its 64-row tiles still give every CU
     // several workgroups, otherwise the 32-row shape (small images: 256x256 has only 4 x 4 tall tiles per image)
     int shape = forced;
@@ -2777,7 +3040,12 @@ static hipError_t launch_gray(const float* in, const float* vg, const float* hor
         switch (shape) {
             case 3: return launch_gray_v<MODE, 4, 16, 2, true, 2, true>(in, vg, hor, out, a, s, fa);
             case 7: return launch_gray_v<MODE, 4, 4, 3, false, 2, true>(in, vg, hor, out, a, s, fa);
-            default: return launch_gray_v<MODE, 4, 8, 3, false, 2, true>(in, vg, hor, out, a, s, fa);
+            default:
+                if constexpr (MODE == 2) {   // the row-pair form (sepconv_gray_mfma_pair): half the LDS operand reads
+                    const bool two_per_cu = a.B * a.tiles_x * ((a.H + 63) / 64) >= 512;   // 64-row tiles, 256 CUs
+                    if (pair == 2 || (pair == 1 && two_per_cu)) return launch_gray_pair_v<4, 16, 2>(in, vg, hor, out, a, s, fa);
+                }
+                return launch_gray_v<MODE, 4, 8, 3, false, 2, true>(in, vg, hor, out, a, s, fa);
         }
     }
     switch (shape) {
