@@ -61,8 +61,51 @@
 #ifndef SSTEM_PAIR_COEF_AUX
 #define SSTEM_PAIR_COEF_AUX 2 // the same bits for the row-pair fused apply (blocked coefficients only): nt, -3.8 % at C2 (profiles/r06)
 #endif
+#ifndef SSTEM_HP_T0       // multi-pass row-pair fused apply (sepconv_gray_mfma_pair_hp): A tiles of passes 0, 1 and 2 (set all three); if they
+#define SSTEM_HP_T0 4     // leave any of the 14, a fourth pass takes the rest.  The B-operand refills are spread over the last pass, so it
+#define SSTEM_HP_T1 4     // should be the longest the registers allow: 4 + 4 + 6 in three passes spills (profiles/r07), hence 4 + 4 + 2 + 4
+#define SSTEM_HP_T2 2
+#endif
+#ifndef SSTEM_HP_VEARLY
+#define SSTEM_HP_VEARLY 16 // the same kernel: at most so many slots of the vertical set that a pass leaves free take the next pass's first taps already
+#endif
+#ifndef SSTEM_HP_PHASE_CT
+#define SSTEM_HP_PHASE_CT 1 // the same kernel: 1 = one copy of the pair loop per phase (phase 0 holds no parked-sum code), 0 = one loop, branches
+#endif
+#ifndef SSTEM_PAIR_STAMP
+#define SSTEM_PAIR_STAMP 0 // developer build (tools/pair_stamps.py), never the product: wave 0 of every workgroup of the row-pair kernels writes
+                           // s_memtime at five points of each pair into a debug buffer (sstem_debug_pair_stamps reads it back)
+#endif
 
 namespace sstem {
+
+#if SSTEM_PAIR_STAMP
+constexpr int PAIR_STAMP_WGS = 2048;          // workgroups recorded (the C2 launch has 2048)
+constexpr int PAIR_STAMP_PER_WG = 2 * 8 * 5;  // phases x pairs of wave 0 x points
+__device__ unsigned long long g_pair_stamps[PAIR_STAMP_WGS * PAIR_STAMP_PER_WG];
+#endif
+__device__ __forceinline__ bool pair_stamp_on(int wave)
+{
+#if SSTEM_PAIR_STAMP
+    return wave == 0 && blockIdx.x < (unsigned)PAIR_STAMP_WGS;
+#else
+    return false;
+#endif
+}
+// point P (0 pair start, 1 first MFMA, 2 / 3 two marks inside the pair, 4 pair end) of pair `pair` of phase `ph`; `on`: wave 0 of a
+// recorded workgroup.  Compiles to nothing in the product build.
+template <int P>
+__device__ __forceinline__ void pair_stamp(bool on, int ph, int pair)
+{
+#if SSTEM_PAIR_STAMP
+    __builtin_amdgcn_sched_barrier(0);
+    if (on) {
+        const unsigned long long t = __builtin_amdgcn_s_memtime();
+        if ((threadIdx.x & 63) == 0) g_pair_stamps[(size_t)blockIdx.x * PAIR_STAMP_PER_WG + (ph * 8 + pair) * 5 + P] = t;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+}
 
 constexpr int F = 51;          // filter taps (reference: FILTER_LENGTH, kernel.cu:9)
 constexpr int KSTEPS = 54;     // 51 taps + 3 skew positions of a 4-pixel block
@@ -1191,6 +1234,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma_pair(
     auto rowoff = [&](int64_t y) __attribute__((always_inline)) -> uint32_t { return (uint32_t)clampy(y) * seg_row + seg_x; };
 
     float hA[KSTEPS], hB[KSTEPS], vA[F], vB[F];
+    const bool stamp = pair_stamp_on(wave);
 
     // taps fy in [f0, f1) of one row, offset ro: (tap 0, row, x0); tap stride ps (0: re-read one hot segment, results unused)
     auto vload = [&](float (&v)[F], rsrc_t r, uint32_t ro, uint32_t ps, const int f0, const int f1) __attribute__((always_inline)) {
@@ -1265,6 +1309,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma_pair(
             float* dstB = out + (b * H + clampy(y + YSTEP)) * W + x0;
             pin_uniform(dstA);
             pin_uniform(dstB);
+            pair_stamp<0>(stamp, ph, rr >> 1);
             const float parkedA = *stg_ptr(dstA, xoff);                  // the first image's channel sums (second phase), requested
             const float parkedB = *stg_ptr(dstB, xoff);                  // early: their waits do not drain the refills behind them
 
@@ -1272,6 +1317,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma_pair(
                 skew_taps_in_place(hA, sub);
                 skew_taps_in_place(hB, sub);
             }
+            pair_stamp<1>(stamp, ph, rr >> 1);
             const float* arow = lds + (yl + sub) * RS + blk * 4;
             f32x4 ar[2][NA];
 #pragma unroll
@@ -1279,6 +1325,8 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma_pair(
             float oA = 0.f, oB = 0.f;
             static_for<0, NGRP>([&](auto kc) __attribute__((always_inline)) {
                 constexpr int k = decltype(kc)::value;
+                if constexpr (k == 1) pair_stamp<2>(stamp, ph, rr >> 1);
+                if constexpr (k == NGRP - 1) pair_stamp<3>(stamp, ph, rr >> 1);
                 if (k + LV < NGRP) vload_group(k + LV, rv_cur, curA, curB, TAP);
                 else vload_group(k + LV - NGRP, rv_n, nxtA, nxtB, pn);
                 // chain (row y, A tile 2k + c) exists for 2k + c <= 12, chain (row y + 4, A tile 2k + c) for 2k + c >= 1
@@ -1348,8 +1396,285 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma_pair(
                     if (ph && fa.out_u8) fa.out_u8[(b * H + y + YSTEP) * W + x0 + lane] = numpy_u8_of(resB);
                 }
             }
+            pair_stamp<4>(stamp, ph, rr >> 1);
         }
     }
+}
+// ---- trusted-gray fused apply, row pairs in a few passes (blocked coefficients) -------------------------------------------------
+// The same work as sepconv_gray_mfma_pair -- per pair 196 ds_read_b128, each feeding row y's tile a and row y + 4's tile a - 1, and the
+// same k-ordered chains and fy-ascending vertical sums, hence the same bits -- in another order, chosen for the coefficient requests:
+//   * the 14 A tiles are split into HP_NP passes (SSTEM_HP_T0 / T1 / T2 / the rest: 4 + 4 + 2 + 4).  Inside a pass the k-chunk
+//     q = 0..13 is the OUTER loop and the pass's tiles the inner one, two tiles (four independent chains, 16 MFMAs) per step, so all
+//     chains of the pass are alive at once;
+//   * both B operands stay resident.  Pass 0 applies the skew chunk by chunk, just before the chunk's MFMAs (three raw taps per row are
+//     carried in registers, the same selects on the same values as skew_taps_in_place); the last pass re-requests entries 4q..4q+3 of
+//     both rows for the next pair right after chunk q, their last reader: 8 loads per chunk, every entry most of a pair ahead of its use;
+//   * one ring of vertical-tap registers holds the taps of the current pass; they are requested a few per chunk over the pass's first
+//     chunks (the registers are dead since the previous pass's vertical stage) and combined at the pass's end.  Registers the previous
+//     pass did not need take their taps during that pass already (hp_vearly);
+//   * A operands through a 2-deep register ring of such steps that runs across chunk and pass boundaries;
+//   * the pair loop exists once per phase (SSTEM_HP_PHASE_CT): the first phase has no parked-sum load, no mean and no u8 store; the
+//     parked sums and the results go through buffer resources like the coefficients.
+// No request burst and no pair-start drain.  The only s_waitcnt vmcnt(0) in the pair loop is the one for the last vertical tap of
+// pass 1, which is the newest request the wave has at that point (issued ten chunks earlier): it drains nothing.
+constexpr int HP_NP = (SSTEM_HP_T0 + SSTEM_HP_T1 + SSTEM_HP_T2 < 14) ? 4 : 3;
+constexpr int hp_a0(int h)
+{
+    return h <= 0 ? 0 : (h == 1 ? SSTEM_HP_T0 : (h == 2 ? SSTEM_HP_T0 + SSTEM_HP_T1 : (h < HP_NP ? SSTEM_HP_T0 + SSTEM_HP_T1 + SSTEM_HP_T2 : 14)));
+}
+constexpr int hp_nt(int h) { return hp_a0(h + 1) - hp_a0(h); }
+constexpr int hp_min(int a, int b) { return a < b ? a : b; }
+constexpr int hp_max(int a, int b) { return a > b ? a : b; }
+// vertical taps of pass h: row y fy in [fa0, fa1) (tiles a <= 12), row y + 4 fy in [fb0, fb1) (tiles a - 1, a >= 1)
+constexpr int hp_fa0(int h) { return 4 * hp_a0(h); }
+constexpr int hp_fa1(int h) { return hp_min(4 * hp_a0(h + 1), F); }
+constexpr int hp_fb0(int h) { return 4 * hp_max(hp_a0(h) - 1, 0); }
+constexpr int hp_fb1(int h) { return hp_min(4 * (hp_a0(h + 1) - 1), F); }
+constexpr int hp_nv(int h) { return (hp_fa1(h) - hp_fa0(h)) + (hp_fb1(h) - hp_fb0(h)); }
+constexpr int HP_NV = hp_max(hp_max(hp_nv(0), hp_nv(1)), hp_max(hp_nv(2), hp_nv(3)));   // (a pass beyond the last has no taps)
+// The set is a ring: pass h's slot i is register (hp_vbase(h) + i) % HP_NV, and a pass starts where the one before it ended.  The
+// HP_NV - hp_nv(h - 1) registers that pass h - 1 does not use are therefore pass h's first slots: they are requested during pass h - 1
+// (hp_vearly(h) of them), which takes them out of the last pass, where the B refills already fill the request queue.
+constexpr int hp_vbase(int h) { return h <= 0 ? 0 : (hp_vbase(h - 1) + hp_nv(h - 1)) % HP_NV; }
+constexpr int hp_vearly(int h) { return (h >= 1 && h < HP_NP) ? hp_min(hp_min(hp_nv(h), HP_NV - hp_nv(h - 1)), SSTEM_HP_VEARLY) : 0; }
+constexpr int HP_EPC = 4;   // early requests per chunk, after the pass's own
+// requests of the vertical set per chunk: the last pass also carries the B refills (8 per chunk)
+constexpr int hp_vpc(int h) { return h == HP_NP - 1 ? 6 : 8; }
+constexpr int hp_vown_chunks(int h) { return (hp_nv(h) - hp_vearly(h) + hp_vpc(h) - 1) / hp_vpc(h); }
+// A-operand read number s = 0..195 of a pair (pass-major, then chunk, then tile): dword offset from the lane's row pointer
+constexpr int hp_read_off(int s, int rs)
+{
+    int h = 0;
+    while (h + 1 < HP_NP && s >= 14 * hp_a0(h + 1)) ++h;
+    const int i = s - 14 * hp_a0(h);
+    return (hp_a0(h) + i % hp_nt(h)) * 4 * rs + (i / hp_nt(h)) * 4;
+}
+constexpr bool hp_split_ok()
+{
+    for (int h = 0; h < HP_NP; ++h)   // every pass takes its A tiles two at a time; its vertical requests fit its chunks
+        if (hp_nt(h) <= 0 || hp_nt(h) % 2 != 0 || hp_vown_chunks(h) * HP_EPC + hp_vearly(h + 1) > 14 * HP_EPC) return false;
+    return hp_a0(HP_NP) == 14 && hp_a0(HP_NP - 1) < 14;
+}
+static_assert(hp_split_ok(), "tile split");
+
+template <int WAVES, int RPW, int WPE>
+__global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma_pair_hp(
+    const float* __restrict__ in_a, const float* __restrict__ ver_a, const float* __restrict__ hor_a,
+    float* __restrict__ out, TileArgs args, FusedArgs fa)
+{
+    static_assert(WAVES == 4, "the rows of a pair are one 4-row MFMA tile apart");
+    static_assert(RPW % 2 == 0, "row pairs");
+    if (fa.gray_flag && *fa.gray_flag == 0) return;   // not identical: the generic build owns this call
+    constexpr int TR = WAVES * RPW;
+    constexpr int ROWS = TR + F;          // +50 halo +1 pad row
+    constexpr int RS = rm_pitch(1);
+    constexpr int YSTEP = WAVES;
+    constexpr int NRD = 14 * 14;          // A-operand reads per pair
+    constexpr int RING = 2;               // A-operand register ring, in steps of two tiles
+    constexpr uint32_t TAP = 256u;        // bytes between consecutive taps of one row segment
+    constexpr int AUX = SSTEM_PAIR_COEF_AUX;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+
+    int64_t b, ty, tx;
+    decode_block(args, b, ty, tx);
+    const int64_t H = args.H, W = args.W;
+    const int64_t plane = H * W;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t y0 = ty * TR, x0 = tx * 64;
+
+    const int lane = threadIdx.x & 63;
+    const int blk = lane >> 2, sub = lane & 3;
+    const bool xok = (x0 + lane) < W;
+    const uint32_t xoff = (uint32_t)(xok ? lane : 0) * 4u;
+    auto clampy = [&](int64_t y) __attribute__((always_inline)) -> int64_t { return y < H ? y : H - 1; };
+    const int64_t yfirst = clampy(y0 + wave);
+
+    const uint32_t seg_row = (uint32_t)args.tiles_x * (uint32_t)(F * 256);
+    const uint32_t img_bytes = (uint32_t)H * seg_row;
+    const int64_t img_elems = (int64_t)(img_bytes >> 2);
+    const uint32_t seg_x = (uint32_t)tx * (uint32_t)(F * 256);
+    auto rowoff = [&](int64_t y) __attribute__((always_inline)) -> uint32_t { return (uint32_t)clampy(y) * seg_row + seg_x; };
+    const bool m1 = sub >= 1, m2 = sub >= 2, m3 = sub == 3;
+    const bool stamp = pair_stamp_on(wave);
+    // the image's output plane(s) as buffer resources: scalar row offset + the lane's byte offset, like the coefficient streams (no
+    // per-lane 64-bit addresses held across the pair, one kind of memory instruction in the loop)
+    const rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(out + b * plane, 0, (int)((uint32_t)plane * 4u), 0x00020000);
+    const rsrc_t rout8 = __builtin_amdgcn_make_buffer_rsrc(fa.out_u8 ? fa.out_u8 + b * plane : nullptr, 0, fa.out_u8 ? (int)(uint32_t)plane : 0, 0x00020000);
+
+    float hA[KSTEPS], hB[KSTEPS], v[HP_NV];
+
+    // slots [i0, i1) of pass h's vertical set, from the rows at roA (row y) and roB (row y + 4)
+    auto vreq = [&](auto hc, rsrc_t r, uint32_t roA, uint32_t roB, const int i0, const int i1) __attribute__((always_inline)) {
+        constexpr int h = decltype(hc)::value;
+        constexpr int nA = hp_fa1(h) - hp_fa0(h), n = hp_nv(h), vb = hp_vbase(h);
+        uint32_t so = roA + (uint32_t)(hp_fa0(h) + i0) * TAP;
+        pin_s(so);
+#pragma unroll
+        for (int i = 0; i < HP_NV; ++i) {
+            if (i < i0 || i >= i1 || i >= nA) continue;
+            v[(vb + i) % HP_NV] = bldc<false, AUX>(r, xoff, so);
+            so += TAP;
+            pin_s(so);
+        }
+        so = roB + (uint32_t)(hp_fb0(h) + (i0 > nA ? i0 - nA : 0)) * TAP;
+        pin_s(so);
+#pragma unroll
+        for (int i = 0; i < HP_NV; ++i) {
+            if (i < i0 || i >= i1 || i < nA || i >= n) continue;
+            v[(vb + i) % HP_NV] = bldc<false, AUX>(r, xoff, so);
+            so += TAP;
+            pin_s(so);
+        }
+    };
+    auto hload = [&](float (&h)[KSTEPS], rsrc_t r, uint32_t ro, uint32_t ps, const int t0, const int t1) __attribute__((always_inline)) {
+        load_taps_buf<false, AUX>(h, r, ro, ps, xoff, t0 < F ? t0 : F, t1 < F ? t1 : F);
+    };
+    {   // raw B operands of my first pair (phase 0); the rest arrive through the refills below
+        const rsrc_t rh = coef_rsrc_c<false>(hor_a, b * img_elems, img_bytes);
+        hload(hA, rh, rowoff(yfirst), TAP, 0, KSTEPS);
+        hload(hB, rh, rowoff(yfirst + YSTEP), TAP, 0, KSTEPS);
+    }
+
+    auto phase = [&](auto phc) __attribute__((always_inline)) {
+        const int ph = phc;               // a constant in each copy when SSTEM_HP_PHASE_CT
+        const float* in = ph ? fa.in2 : in_a;
+        const float* ver = ph ? fa.ver2 : ver_a;
+        const float* hor = ph ? fa.hor2 : hor_a;
+        const bool next_ph = ph == 0;
+        const rsrc_t rv_cur = coef_rsrc_c<false>(ver, b * img_elems, img_bytes);
+        const rsrc_t rh_cur = coef_rsrc_c<false>(hor, b * img_elems, img_bytes);
+        const rsrc_t rh_nxt = coef_rsrc_c<false>(next_ph ? fa.hor2 : hor, b * img_elems, img_bytes);
+
+        if (ph) __syncthreads();          // every wave is done reading the first image's tile
+        stage_gray_tile_dma<WAVES * 64, ROWS, RS, true>(lds, in + (b * args.in_planes) * plane, (int)H, (int)W, (int)y0, (int)x0);
+        __syncthreads();
+
+        int nrows = 0;                      // rows of this tile that are mine (wave-uniform)
+        if (y0 + wave < H) {
+            const int64_t left = (H - 1 - (y0 + wave)) / YSTEP + 1;
+            nrows = left < RPW ? (int)left : RPW;
+        }
+#pragma unroll 1
+        for (int rr = 0; rr < nrows; rr += 2) {
+            const bool more = rr + 2 < nrows;                            // is there a next pair in this phase?
+            const bool two = rr + 1 < nrows;                             // is the pair's second row inside the image?
+            const int yl = wave + rr * YSTEP;
+            const int64_t y = y0 + yl;
+            // where the B refills go: my next pair, the second phase's first pair, or (last pair of the launch) one hot segment of my
+            // own row again (tap stride 0)
+            const int64_t ynext = more ? (y + 2 * YSTEP) : (next_ph ? yfirst : y);
+            const uint32_t pn = (more || next_ph) ? TAP : 0u;
+            const uint32_t curA = rowoff(y), curB = rowoff(y + YSTEP);
+            const uint32_t nxtA = rowoff(ynext), nxtB = rowoff(ynext + YSTEP);
+            const rsrc_t rh_n = more ? rh_cur : rh_nxt;
+            uint32_t dstA = (uint32_t)(y * W + x0) * 4u;                  // byte offsets into the image's output plane
+            uint32_t dstB = (uint32_t)(clampy(y + YSTEP) * W + x0) * 4u;
+            pin_s(dstA);
+            pin_s(dstB);
+            pair_stamp<0>(stamp, ph, rr >> 1);
+            float parkedA = 0.f, parkedB = 0.f;                          // the first image's channel sums: second phase only
+            if (ph) {
+                parkedA = bld<0>(rout, xoff, dstA);
+                parkedB = bld<0>(rout, xoff, dstB);
+            }
+            const float* arow = lds + (yl + sub) * RS + blk * 4;
+            f32x4 ar[RING][2];
+#pragma unroll
+            for (int d = 0; d < 2; ++d) ar[0][d] = *reinterpret_cast<const f32x4*>(arow + hp_read_off(d, RS));
+            float oA = 0.f, oB = 0.f;
+            float cA0 = 0.f, cA1 = 0.f, cA2 = 0.f, cB0 = 0.f, cB1 = 0.f, cB2 = 0.f;   // raw taps t - 3, t - 2, t - 1
+            static_for<0, HP_NP>([&](auto hc) __attribute__((always_inline)) {
+                constexpr int h = decltype(hc)::value;
+                constexpr int NT = hp_nt(h), A0 = hp_a0(h), VPC = hp_vpc(h), E = hp_vearly(h), CO = hp_vown_chunks(h), VB = hp_vbase(h);
+                if constexpr (h == 1) pair_stamp<2>(stamp, ph, rr >> 1);   // (marks 2 and 3: the start of pass 1 and of the last pass)
+                if constexpr (h == HP_NP - 1) pair_stamp<3>(stamp, ph, rr >> 1);
+                f32x4 accA[NT], accB[NT];
+#pragma unroll
+                for (int c = 0; c < NT; ++c) { accA[c] = (f32x4){0.f, 0.f, 0.f, 0.f}; accB[c] = accA[c]; }
+                static_for<0, 14>([&](auto qc) __attribute__((always_inline)) {
+                    constexpr int q = decltype(qc)::value;
+                    if constexpr (q < CO) vreq(hc, rv_cur, curA, curB, E + VPC * q, E + VPC * q + VPC);
+                    else if constexpr (HP_EPC * (q - CO) < hp_vearly(h + 1))
+                        vreq(std::integral_constant<int, h + 1>{}, rv_cur, curA, curB, HP_EPC * (q - CO), hp_min(HP_EPC * (q - CO) + HP_EPC, hp_vearly(h + 1)));
+                    if constexpr (h == 0) {   // entries 4q .. 4q + 3 of both B operands from the raw taps (waits for these only)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const int t = 4 * q + e;
+                            if (t < KSTEPS) {
+                                const float rA = (t < F) ? hA[t] : 0.f, rB = (t < F) ? hB[t] : 0.f;
+                                hA[t] = m3 ? cA0 : (m2 ? cA1 : (m1 ? cA2 : rA));
+                                hB[t] = m3 ? cB0 : (m2 ? cB1 : (m1 ? cB2 : rB));
+                                cA0 = cA1; cA1 = cA2; cA2 = rA;
+                                cB0 = cB1; cB1 = cB2; cB2 = rB;
+                            }
+                        }
+                        if constexpr (q == 0) pair_stamp<1>(stamp, ph, rr >> 1);
+                    }
+#pragma unroll
+                    for (int c = 0; c < NT; c += 2) {                    // a step: two A tiles, four independent chains
+                        const int s = 14 * A0 + q * NT + c;              // read number of the step's first tile: ring slot (s / 2) % RING
+                        if (s + 2 < NRD) {
+#pragma unroll
+                            for (int d = 0; d < 2; ++d)
+                                ar[(s / 2 + 1) % RING][d] = *reinterpret_cast<const f32x4*>(arow + hp_read_off(s + 2 + d, RS));
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const int t = 4 * q + e;
+                            if (t < KSTEPS) {
+#pragma unroll
+                                for (int d = 0; d < 2; ++d) {
+                                    const int a = A0 + c + d;
+                                    if (a <= 12) accA[c + d] = __builtin_amdgcn_mfma_f32_4x4x1f32(ar[(s / 2) % RING][d][e], hA[t], accA[c + d], 0, 0, 0);
+                                    if (a >= 1) accB[c + d] = __builtin_amdgcn_mfma_f32_4x4x1f32(ar[(s / 2) % RING][d][e], hB[t], accB[c + d], 0, 0, 0);
+                                }
+                            }
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    if constexpr (h == HP_NP - 1) {                      // entries 4q .. 4q + 3 are done: the next pair's B operands
+                        hload(hA, rh_n, nxtA, pn, 4 * q, 4 * q + 4);
+                        hload(hB, rh_n, nxtB, pn, 4 * q, 4 * q + 4);
+                    }
+                });
+                {   // vertical stage of this pass, fy ascending in both sums
+                    constexpr int fa0 = hp_fa0(h), fb0 = hp_fb0(h), nA = hp_fa1(h) - hp_fa0(h);
+#pragma unroll
+                    for (int c = 0; c < NT; ++c)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if (A0 + c <= 12 && 4 * (A0 + c) + i < F) oA = fmaf(v[(VB + 4 * (A0 + c) + i - fa0) % HP_NV], accA[c][i], oA);
+#pragma unroll
+                    for (int c = 0; c < NT; ++c)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if (A0 + c >= 1 && 4 * (A0 + c - 1) + i < F) oB = fmaf(v[(VB + nA + 4 * (A0 + c - 1) + i - fb0) % HP_NV], accB[c][i], oB);
+                }
+                asm volatile("" : "+v"(oA), "+v"(oB));   // here, not sunk to the stores: the accumulators and taps die now
+            });
+            if (xok) {   // channel sum, then the mean over channels of both images (model_interp.py:94-97)
+                const float csA = (oA + oA) + oA;
+                const float resA = ph ? (parkedA + csA) * (1.0f / 3) : csA;
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, resA), rout, (int)xoff, (int)dstA, 0);
+                if (ph && fa.out_u8) __builtin_amdgcn_raw_buffer_store_b8(numpy_u8_of(resA), rout8, (int)(xoff >> 2), (int)(dstA >> 2), 0);
+                if (two) {
+                    const float csB = (oB + oB) + oB;
+                    const float resB = ph ? (parkedB + csB) * (1.0f / 3) : csB;
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, resB), rout, (int)xoff, (int)dstB, 0);
+                    if (ph && fa.out_u8) __builtin_amdgcn_raw_buffer_store_b8(numpy_u8_of(resB), rout8, (int)(xoff >> 2), (int)(dstB >> 2), 0);
+                }
+            }
+            pair_stamp<4>(stamp, ph, rr >> 1);
+        }
+    };
+#if SSTEM_HP_PHASE_CT
+    phase(std::integral_constant<int, 0>{});
+    phase(std::integral_constant<int, 1>{});
+#else
+#pragma unroll 1
+    for (int ph = 0; ph < 2; ++ph) phase(ph);
+#endif
 }
 
 // ---- fused apply on grayscale planes, 16x16x4 formulation (round 5) -------------------------------------------------------------
@@ -2987,25 +3312,27 @@ static hipError_t launch_gray_v(const float* in, const float* ver, const float* 
     return hipGetLastError();
 }
 
-// Row-pair form of the blocked fused apply (sepconv_gray_mfma_pair, 4 waves x 16 rows, 2 waves per SIMD).  Developer knob
-// SSTEM_GRAY_PAIR, read once, at the first trusted-gray launch of any kind: 0 = always the one-row kernel, 1 = the pair form when its
-// grid gives every CU at least two workgroups (default), 2 = always the pair form (A/B runs, tests).  At C2, same box: 1.319 ms against
-// 1.340 for the one-row kernel; a 4 x 8 pair form ran 1.340 -- two waves per SIMD need the taller tile's rows in flight, which a grid
-// of one workgroup per CU does not give (profiles/r06).
+// Row-pair forms of the blocked fused apply (4 waves x 16 rows, 2 waves per SIMD): sepconv_gray_mfma_pair (group by group) and
+// sepconv_gray_mfma_pair_hp (the same pair in four passes with the k-chunk as the outer loop: no request burst).
+// Developer knob SSTEM_GRAY_PAIR, read once, at the first trusted-gray launch of any kind: 0 = always the one-row kernel, 1 = the
+// multi-pass pair form when its grid gives every CU at least two workgroups (default), 2 = always the group-by-group pair form, 3 =
+// always the multi-pass pair form (A/B runs, tests).  At C2, same box, alternating: 1.2920 ms (group by group) against 1.2653
+// (multi-pass), -2.1 %; the one-row kernel ran 1.340 against 1.319 for the group-by-group form; a 4 x 8 pair form ran 1.340 -- two waves
+// per SIMD need the taller tile's rows in flight, which a grid of one workgroup per CU does not give (profiles/r06, profiles/r07).
 static int gray_pair_variant()
 {
     static const int v = [] { const char* e = getenv("SSTEM_GRAY_PAIR"); return e ? atoi(e) : 1; }();
     return v;
 }
 
-template <int WAVES, int RPW, int WPE>
+template <int WAVES, int RPW, int WPE, bool HP = false>
 static hipError_t launch_gray_pair_v(const float* in, const float* ver, const float* hor, float* out, TileArgs a,
                                      hipStream_t s, const FusedArgs& fa)
 {
     constexpr int TR = WAVES * RPW;
     constexpr size_t lds_bytes = (size_t)(TR + F) * rm_pitch(1) * sizeof(float);
     static_assert(lds_bytes * WPE <= 160 * 1024, "LDS");
-    auto k = sepconv_gray_mfma_pair<WAVES, RPW, WPE>;
+    auto k = HP ? sepconv_gray_mfma_pair_hp<WAVES, RPW, WPE> : sepconv_gray_mfma_pair<WAVES, RPW, WPE>;
     static std::atomic<uint64_t> lds_set{0};
     const hipError_t attr = set_lds(k, lds_bytes, lds_set);
     if (attr != hipSuccess) return attr;
@@ -3043,7 +3370,8 @@ static hipError_t launch_gray(const float* in, const float* vg, const float* hor
             default:
                 if constexpr (MODE == 2) {   // the row-pair form (sepconv_gray_mfma_pair): half the LDS operand reads
                     const bool two_per_cu = a.B * a.tiles_x * ((a.H + 63) / 64) >= 512;   // 64-row tiles, 256 CUs
-                    if (pair == 2 || (pair == 1 && two_per_cu)) return launch_gray_pair_v<4, 16, 2>(in, vg, hor, out, a, s, fa);
+                    if (pair == 3 || (pair == 1 && two_per_cu)) return launch_gray_pair_v<4, 16, 2, true>(in, vg, hor, out, a, s, fa);
+                    if (pair == 2) return launch_gray_pair_v<4, 16, 2>(in, vg, hor, out, a, s, fa);
                 }
                 return launch_gray_v<MODE, 4, 8, 3, false, 2, true>(in, vg, hor, out, a, s, fa);
         }
@@ -3493,3 +3821,14 @@ hipError_t launch_interp_fused_gray_bf16coef(const float* g1, const float* g2, c
 }
 
 }  // namespace sstem
+
+#if SSTEM_PAIR_STAMP
+// developer builds only: the s_memtime stamps of the row-pair kernels' last launch ([workgroup][phase][pair][point], 0 = not written)
+extern "C" int sstem_debug_pair_stamps(unsigned long long* out, long long n)
+{
+    const size_t total = (size_t)sstem::PAIR_STAMP_WGS * sstem::PAIR_STAMP_PER_WG;
+    if (n < 0 || (size_t)n > total) return -1;
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(sstem::g_pair_stamps), (size_t)n * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
+}
+#endif
