@@ -35,25 +35,11 @@
 
 #include "sepconv_kernels.h"
 
-#ifndef SSTEM_ABLATE
-#define SSTEM_ABLATE 0   // developer builds (trusted-gray kernel): 1 no H loads, 2 no V loads, 4 no tile staging, 8 no MFMAs / LDS reads
-#endif
 #ifndef SSTEM_HPF
 #define SSTEM_HPF 11     // trusted-gray kernel, B-operand prefetch: next-row horizontal taps requested per MFMA group (11: all by group 4)
 #endif
-#ifndef SSTEM_BLK_SKEWLD
-#define SSTEM_BLK_SKEWLD 0 // blocked coefficients: 1 = the B operand's taps are requested already skewed (load_taps_skewed_buf) instead of coalesced
-                           // requests + the in-register skew.  Measured and left off: -0.5 % on the 64-row shape, +3 % on the 32-row default
-                           // (profiles/r03/a_*): the ~150 VALU instructions per pixel row it removes were not what the kernel waits for
-#endif
-#ifndef SSTEM_GRAY_DMA
-#define SSTEM_GRAY_DMA 1 // trusted-gray forward / fused-apply kernel: tile staging by LDS-DMA (0: through registers, the round-1 loader)
-#endif
 #ifndef SSTEM_RGB_RING
 #define SSTEM_RGB_RING 2 // three-channel streaming kernel: A-operand register ring (2: one chunk = 12 MFMAs of LDS latency covered; 3: two)
-#endif
-#ifndef SSTEM_GRAY16_ABLATE
-#define SSTEM_GRAY16_ABLATE 0 // 1: the timing-only ablation variants of sepconv_gray16_mfma (SSTEM_GRAY16_VAR) are compiled in
 #endif
 #ifndef SSTEM_COEF_AUX
 #define SSTEM_COEF_AUX 0   // cache-policy bits of the coefficient loads of the trusted-gray kernel (gfx950: 1 sc0, 2 nt, 16 sc1)
@@ -118,14 +104,10 @@ constexpr int TILE_COLS = 116; // 64 pixels + 50 halo, rounded up to whole 16-B 
 // {0,3,5,6}, {1,2,4,7} (+8), whose pairwise differences are never 4, 8 or 12 -- conflict-free,
 // and every address is ONE base register + an immediate offset.
 __host__ __device__ constexpr int rm_pitch(int ch) { return ch == 2 ? 120 : 144; }
-// Tall tiles (16 waves x 3 rows) only fit in 160 KB with the unpadded pitch: a few 2-way conflicts on
-// the A reads (LDS is ~27 % busy in this kernel) in exchange for 1.5x more rows per staged halo.
-__host__ __device__ constexpr int rm_pitch_tile(int ch, int waves, int rpw)
-{
-    return (waves * rpw > 36) ? TILE_COLS : rm_pitch(ch);
-}
 static_assert((1 * rm_pitch(1) / 4) % 16 == 4 && (2 * rm_pitch(2) / 4) % 16 == 12 &&
               (3 * rm_pitch(3) / 4) % 16 == 12 && rm_pitch(2) >= TILE_COLS, "LDS row stride");
+// LDS bytes of the row-major image of a tile of tr output rows: + 50 halo rows + 1 pad row, ch channels
+constexpr size_t rm_lds_bytes(int ch, int tr) { return (size_t)ch * (tr + F) * rm_pitch(ch) * sizeof(float); }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -357,9 +339,6 @@ __device__ __forceinline__ void load_skewed(float (&dst)[N], const float* row_ba
 #pragma unroll
     for (int t = 0; t < N; ++t) {
         if (t < t0 || t >= t1) continue;
-#if SSTEM_ABLATE & 1
-        dst[t] = 0.25f; continue;
-#endif
         if (t >= F + 3) { dst[t] = 0.f; continue; }              // t - shift >= 51 for every shift
         if (t >= 3 && t < F) {
             const float v = ldg(ub, skew_off);
@@ -421,7 +400,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void sepconv_rowmajor_mfma(
     constexpr int TR = WAVES * RPW;
     constexpr int ROWS = TR + F;          // +50 halo +1 pad row (fy = 51, coefficient 0)
     constexpr int CHL = CH;               // channels staged in LDS
-    constexpr int P = rm_pitch_tile(CHL, WAVES, RPW);   // dwords between channels of one row
+    constexpr int P = rm_pitch(CHL);      // dwords between channels of one row
     constexpr int RS = CHL * P;           // dwords between rows
     constexpr int RING = (WAVES >= 16) ? 2 : 3;   // A-operand register ring (see below)
     constexpr int VQD = (WAVES >= 16) ? 1 : 3;    // vertical-coefficient queue depth (16 waves: deeper queues measured no faster)
@@ -461,7 +440,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void sepconv_rowmajor_mfma(
 
     if (MODE == 2 && ph) __syncthreads();      // every wave is done reading the first image's tile
     bool same = false;
-    if (!(args.dbg & 1) && !(SSTEM_ABLATE & 4)) {
+    if (!(args.dbg & 1)) {
         if (MODE == 2) {
             // the clamped per-thread offsets do not depend on the phase: keep the compiler from hoisting them
             // out of the phase loop (they would stay live across both images' MFMA loops and spill)
@@ -548,11 +527,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void sepconv_rowmajor_mfma(
                     const float* vt = vp + (int64_t)((fg + 1) * 8) * plane;
 #pragma unroll
                     for (int i = 0; i < 8; ++i)                          // fg == 5: taps 48..50 only (clamped)
-#if SSTEM_ABLATE & 2
-                        vl[i] = 0.5f;
-#else
                         vl[i] = ldg(vt + (int64_t)((fg == 5 && i > 2) ? 2 : i) * plane, xoff);
-#endif
                 }
 #pragma unroll
                 for (int tq = 0; tq < 14; ++tq) {
@@ -593,11 +568,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void sepconv_rowmajor_mfma(
             // would make the wave wait for the load it has just issued)
             float va[8], vbuf[8];
 #pragma unroll
-#if SSTEM_ABLATE & 2
-            for (int i = 0; i < 8; ++i) va[i] = 0.5f;
-#else
             for (int i = 0; i < 8; ++i) va[i] = ldg(vp + (int64_t)i * plane, xoff);
-#endif
 #pragma unroll 1
             for (int fg = 0; fg < 6; fg += 2) { group(fg, va, vbuf); group(fg + 1, vbuf, va); }
             {   // tile 12: rows fy = 48, 49, 50 (+ the pad row); its taps were requested by group 5 into va[0..2]
@@ -789,45 +760,9 @@ __device__ __forceinline__ void load_taps_buf(float (&dst)[KSTEPS], rsrc_t r, ui
 #pragma unroll
     for (int f = 0; f < F; ++f) {
         if (f < t0 || f >= t1) continue;
-#if SSTEM_ABLATE & 1
-        dst[f] = 0.25f; continue;
-#endif
         dst[f] = bldc<BF, AUX>(r, xoff, soff);
         soff += pstride;
         pin_s(soff);
-    }
-}
-
-// Blocked coefficients: entry t of the B operand straight from memory -- lane (block, j) reads tap t - j of its own pixel.  The four taps
-// of one entry are four neighbouring 256-byte runs inside the row segment's 13 KB (in NCHW they would be four planes: eight cache lines
-// from four DRAM pages per instruction, which cost the stream 6-12 %, hence the in-register skew there); no select per entry except
-// for the three entries at either end, whose out-of-range lanes read a valid tap and are zeroed.  t in [t0, t1) (constants after
-// unrolling).  Same values as load_taps_buf + skew_taps_in_place: bit-identical results, ~150 VALU instructions per pixel row less
-// (vector instructions do not co-issue with the 4x4x1 MFMA).
-template <int AUX = SSTEM_COEF_AUX>
-__device__ __forceinline__ void load_taps_skewed_buf(float (&dst)[KSTEPS], rsrc_t r, uint32_t rowoff, uint32_t pstride,
-                                                     uint32_t xoff, int sub, const int t0 = 0, const int t1 = KSTEPS)
-{
-    const uint32_t vo = xoff + (uint32_t)(3 - sub) * pstride;            // interior entries: tap (t - 3) + (3 - sub)
-    uint32_t soff = rowoff + (uint32_t)((t0 > 3 ? t0 : 3) - 3) * pstride;
-    pin_s(soff);
-#pragma unroll
-    for (int t = 0; t < KSTEPS; ++t) {
-        if (t < t0 || t >= t1) continue;
-#if SSTEM_ABLATE & 1
-        dst[t] = 0.25f; continue;
-#endif
-        if (t >= 3 && t < F) {
-            dst[t] = bld<AUX>(r, vo, soff);
-            soff += pstride;
-            pin_s(soff);
-        } else {
-            int f = t - sub;
-            const bool ok = f >= 0 && f < F;
-            f = f < 0 ? 0 : (f > F - 1 ? F - 1 : f);
-            const float v = bld<AUX>(r, xoff + (uint32_t)f * pstride, rowoff);
-            dst[t] = ok ? v : 0.f;
-        }
     }
 }
 
@@ -849,45 +784,11 @@ __device__ __forceinline__ void skew_taps_in_place(float (&h)[KSTEPS], int sub)
     }
 }
 
-// Channel 0 of one image tile -> LDS rows of P dwords, in BATCH-row groups per thread (the trusted-gray kernel
-// holds ~110 coefficient registers while it stages).  REPL: the image is the UNPADDED [Hs, Ws] plane and
-// ReplicationPad2d(25) is folded in (clamped coordinates); otherwise it is the padded plane and elements outside it
-// are zero.  All addressing is 32-bit (H*W < 2^31, checked by the C-ABI).
-template <int THREADS, int ROWS, int P, bool REPL, int BATCH = 11>
-__device__ __forceinline__ void stage_gray_tile(float* lds, const float* __restrict__ img, int Hs, int Ws, int y0, int x0)
-{
-    const int col = threadIdx.x & 127;
-    const int rsub = threadIdx.x >> 7;
-    constexpr int RSTEP = THREADS / 128;
-    constexpr int NPASS = (ROWS + RSTEP - 1) / RSTEP;
-    if (col >= TILE_COLS) return;
-    int xs = x0 + col - (REPL ? F / 2 : 0);
-    const bool col_ok = REPL || xs < Ws;
-    xs = xs < 0 ? 0 : (xs > Ws - 1 ? Ws - 1 : xs);
-    float* dst = lds + col;
-#pragma unroll 1
-    for (int k0 = 0; k0 < NPASS; k0 += BATCH) {
-        float v[BATCH];
-#pragma unroll
-        for (int k = 0; k < BATCH; ++k) {
-            const int r = rsub + (k0 + k) * RSTEP;
-            int ys = y0 + r - (REPL ? F / 2 : 0);
-            const bool ok = col_ok && (REPL || ys < Hs);
-            ys = ys < 0 ? 0 : (ys > Hs - 1 ? Hs - 1 : ys);
-            const float t = ldg(img, ((uint32_t)ys * (uint32_t)Ws + (uint32_t)xs) * 4u);
-            v[k] = ok ? t : 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < BATCH; ++k) {
-            const int r = rsub + (k0 + k) * RSTEP;
-            if (r < ROWS) dst[r * P] = v[k];
-        }
-    }
-}
-
-// The same tile by LDS-DMA (buffer_load ... lds): one 256-byte row piece per wave-instruction straight into LDS, every piece of the
-// tile in flight at once, no registers -- ONE memory latency per tile instead of NPASS / BATCH dependent batches.  Elements outside
-// the image are read from clamped (valid, finite) addresses instead of being zeroed: they only ever meet coefficients of exactly 0.
+// Channel 0 of one image tile -> LDS rows of P dwords by LDS-DMA (buffer_load ... lds): one 256-byte row piece per wave-instruction
+// straight into LDS, every piece of the tile in flight at once, no registers -- ONE memory latency per tile.  REPL: the image is the
+// UNPADDED [Hs, Ws] plane and ReplicationPad2d(25) is folded in (clamped coordinates); otherwise it is the padded plane.  Elements
+// outside the image are read from clamped (valid, finite) addresses instead of being zeroed: they only ever meet coefficients of
+// exactly 0.  All addressing is 32-bit (H*W < 2^31, checked by the C-ABI).
 typedef __attribute__((address_space(3))) float lds_float;
 template <int THREADS, int ROWS, int P, bool REPL>
 __device__ __forceinline__ void stage_gray_tile_dma(float* lds, const float* __restrict__ img, int Hs, int Ws, int y0, int x0)
@@ -990,16 +891,11 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma(
         pin_s(soff);
 #pragma unroll
         for (int k = 0; k < F; ++k) {
-#if SSTEM_ABLATE & 2
-            vs[k] = 0.5f;
-#else
             vs[k] = bldc<BF>(rv, xoff, soff);
             soff += plane4;
             pin_s(soff);
-#endif
         }
-        if constexpr (BLK && SSTEM_BLK_SKEWLD) load_taps_skewed_buf(hs, rh, firstoff, plane4, xoff, sub);
-        else load_taps_buf<BF>(hs, rh, firstoff, plane4, xoff);
+        load_taps_buf<BF>(hs, rh, firstoff, plane4, xoff);
     }
 
 #pragma unroll 1
@@ -1015,15 +911,8 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma(
         const rsrc_t rh_nxt = coef_rsrc_c<BF>(next_ph ? fa.hor2 : hor, b * img_elems, img_bytes);
 
         if (ph) __syncthreads();          // every wave is done reading the first image's tile
-#if !(SSTEM_ABLATE & 4)
-#if SSTEM_GRAY_DMA
         if (MODE == 2) stage_gray_tile_dma<WAVES * 64, ROWS, RS, true>(lds, in + (b * args.in_planes) * plane, (int)H, (int)W, (int)y0, (int)x0);
         else stage_gray_tile_dma<WAVES * 64, ROWS, RS, false>(lds, in + (b * C) * Hin * Win, (int)Hin, (int)Win, (int)y0, (int)x0);
-#else
-        if (MODE == 2) stage_gray_tile<WAVES * 64, ROWS, RS, true>(lds, in + (b * args.in_planes) * plane, (int)H, (int)W, (int)y0, (int)x0);
-        else stage_gray_tile<WAVES * 64, ROWS, RS, false>(lds, in + (b * C) * Hin * Win, (int)Hin, (int)Win, (int)y0, (int)x0);
-#endif
-#endif
         __syncthreads();
 
         // one pixel row: B operand hc, requests the wave's next row into hx (PFH) / back into hc (!PFH)
@@ -1043,8 +932,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma(
             float parked = 0.f;            // MODE 2: the first image's channel sum (second phase), requested now so that its
             if (MODE == 2) parked = *stg_ptr(dst, xoff);   // wait at the row end does not drain the refills behind it
 
-            if constexpr (!(BLK && SSTEM_BLK_SKEWLD)) skew_taps_in_place(hc, sub);       // the raw taps requested a row ago (waits for them here); blocked
-                                                                   // coefficients arrive skewed (load_taps_skewed_buf)
+            skew_taps_in_place(hc, sub);                                 // the raw taps requested a row ago (waits for them here)
             const float* arow = lds + (yl + sub) * RS + blk * 4;
             f32x4 ar[RING][NG];
 #pragma unroll
@@ -1061,9 +949,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma(
                 const float* abase = arow + fg * (NG * 4) * RS;
                 const float* anext = arow + (fg + 1) * (NG * 4) * RS;    // fg == 5: tile 12 (chain 0 only)
                 const int gstep = (fg == 5) ? 0 : 4 * RS;               // keep chain 1 inside the image then
-                if constexpr (PFH && BLK && SSTEM_BLK_SKEWLD) load_taps_skewed_buf(hx, rh, nextoff, pn, xoff, sub, (SSTEM_HPF * fg < KSTEPS) ? SSTEM_HPF * fg : KSTEPS,
-                                                               (SSTEM_HPF * fg + SSTEM_HPF < KSTEPS) ? SSTEM_HPF * fg + SSTEM_HPF : KSTEPS);
-                else if constexpr (PFH) load_taps_buf<BF>(hx, rh, nextoff, pn, xoff, (SSTEM_HPF * fg < F) ? SSTEM_HPF * fg : F,
+                if constexpr (PFH) load_taps_buf<BF>(hx, rh, nextoff, pn, xoff, (SSTEM_HPF * fg < F) ? SSTEM_HPF * fg : F,
                                                  (SSTEM_HPF * fg + SSTEM_HPF < F) ? SSTEM_HPF * fg + SSTEM_HPF : F);   // SSTEM_HPF taps per MFMA group
 #pragma unroll
                 for (int tq = 0; tq < 14; ++tq) {
@@ -1082,13 +968,9 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma(
                     for (int e = 0; e < 4; ++e) {
                         const int t = tq * 4 + e;
                         if (t < KSTEPS) {
-#if SSTEM_ABLATE & 8
-                            if (fg == 0) acc[0][e] += hc[t];
-#else
 #pragma unroll
                             for (int g = 0; g < NG; ++g)
                                 acc[g] = __builtin_amdgcn_mfma_f32_4x4x1f32(ar[cc % RING][g][e], hc[t], acc[g], 0, 0, 0);
-#endif
                         }
                     }
                     __builtin_amdgcn_sched_barrier(0);
@@ -1098,10 +980,8 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma(
 #pragma unroll
                     for (int i = 0; i < 4; ++i) o = fmaf(vs[fg * 8 + g * 4 + i], acc[g][i], o);   // fy ascending
                 asm volatile("" : "+v"(o));   // here, not sunk to the store: the accumulators and taps die now
-#if !(SSTEM_ABLATE & 2)
 #pragma unroll
                 for (int i = 0; i < 8; ++i) { vs[fg * 8 + i] = bldc<BF>(rv, xoff, vrun); vrun += pn; pin_s(vrun); }
-#endif
             }
             {   // tile 12: rows fy = 48, 49, 50 (+ the pad row)
                 f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1114,19 +994,15 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma(
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int t = tq * 4 + e;
-#if !(SSTEM_ABLATE & 8)
                         if (t < KSTEPS) acc0 = __builtin_amdgcn_mfma_f32_4x4x1f32(ar[cc % RING][0][e], hc[t], acc0, 0, 0, 0);
-#endif
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
 #pragma unroll
                 for (int i = 0; i < 3; ++i) o = fmaf(vs[48 + i], acc0[i], o);
                 asm volatile("" : "+v"(o));
-#if !(SSTEM_ABLATE & 2)
 #pragma unroll
                 for (int i = 0; i < 3; ++i) { vs[48 + i] = bldc<BF>(rv, xoff, vrun); vrun += pn; pin_s(vrun); }
-#endif
             }
             if (xok) {
                 if (MODE == 0) {
@@ -1139,8 +1015,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma(
                     if (ph && fa.out_u8) fa.out_u8[(b * H + y) * W + x0 + lane] = numpy_u8_of(res);
                 }
             }
-            if constexpr (!PFH && BLK && SSTEM_BLK_SKEWLD) load_taps_skewed_buf(hc, rh, nextoff, pn, xoff, sub);
-            else if constexpr (!PFH) load_taps_buf<BF>(hc, rh, nextoff, pn, xoff);
+            if constexpr (!PFH) load_taps_buf<BF>(hc, rh, nextoff, pn, xoff);
         };
         int nrows = 0;                      // rows of this tile that are mine (wave-uniform)
         if (y0 + ywave < H) {
@@ -1254,8 +1129,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma_pair(
         vload(vB, r, roB, ps, (8 * k - 4 > 0) ? 8 * k - 4 : 0, (8 * k + 4 < F) ? 8 * k + 4 : F);
     };
     auto hload = [&](float (&h)[KSTEPS], rsrc_t r, uint32_t ro, uint32_t ps, const int t0, const int t1) __attribute__((always_inline)) {
-        if constexpr (SSTEM_BLK_SKEWLD) load_taps_skewed_buf<AUX>(h, r, ro, ps, xoff, sub, t0, t1 < KSTEPS ? t1 : KSTEPS);
-        else load_taps_buf<false, AUX>(h, r, ro, ps, xoff, t0 < F ? t0 : F, t1 < F ? t1 : F);
+        load_taps_buf<false, AUX>(h, r, ro, ps, xoff, t0 < F ? t0 : F, t1 < F ? t1 : F);
     };
     {   // coefficients of my first pair (phase 0); the rest arrive through the refills below
         const rsrc_t rv = coef_rsrc_c<false>(ver_a, b * img_elems, img_bytes);
@@ -1279,11 +1153,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma_pair(
         const rsrc_t rh_nxt = coef_rsrc_c<false>(next_ph ? fa.hor2 : hor, b * img_elems, img_bytes);
 
         if (ph) __syncthreads();          // every wave is done reading the first image's tile
-#if SSTEM_GRAY_DMA
         stage_gray_tile_dma<WAVES * 64, ROWS, RS, true>(lds, in + (b * args.in_planes) * plane, (int)H, (int)W, (int)y0, (int)x0);
-#else
-        stage_gray_tile<WAVES * 64, ROWS, RS, true>(lds, in + (b * args.in_planes) * plane, (int)H, (int)W, (int)y0, (int)x0);
-#endif
         __syncthreads();
 
         int nrows = 0;                      // rows of this tile that are mine (wave-uniform)
@@ -1313,10 +1183,8 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma_pair(
             const float parkedA = *stg_ptr(dstA, xoff);                  // the first image's channel sums (second phase), requested
             const float parkedB = *stg_ptr(dstB, xoff);                  // early: their waits do not drain the refills behind them
 
-            if constexpr (!SSTEM_BLK_SKEWLD) {                           // the raw taps requested during the last pair (waits here)
-                skew_taps_in_place(hA, sub);
-                skew_taps_in_place(hB, sub);
-            }
+            skew_taps_in_place(hA, sub);                                 // the raw taps requested during the last pair (waits here)
+            skew_taps_in_place(hB, sub);
             pair_stamp<1>(stamp, ph, rr >> 1);
             const float* arow = lds + (yl + sub) * RS + blk * 4;
             f32x4 ar[2][NA];
@@ -1702,7 +1570,8 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma_pair_hp(
 // Not bit-identical to the 4x4x1 kernels (another summation order; same products): tests compare it with the oracle at their
 // tolerance and with itself across the two coefficient layouts bit for bit.
 constexpr int G16_RS = 130;       // dwords between tile rows: ds_read_b32 banks (a / 4) mod 32 per 32-lane group -> 2 j + k: conflict-free
-template <int WAVES, int RPW, bool BLK, int VAR = 0>
+constexpr size_t g16_lds_bytes(int tr) { return (size_t)2 * (tr + F) * G16_RS * sizeof(float); }   // both images' tiles are resident
+template <int WAVES, int RPW, bool BLK>
 __global__ __launch_bounds__(WAVES * 64, 2) void sepconv_gray16_mfma(
     const float* __restrict__ in_a, const float* __restrict__ ver_a, const float* __restrict__ hor_a,
     float* __restrict__ out, TileArgs args, FusedArgs fa)
@@ -1811,7 +1680,6 @@ __global__ __launch_bounds__(WAVES * 64, 2) void sepconv_gray16_mfma(
         for (int cg = 0; cg < 4; ++cg) {
             float (&X)[17] = Bh[cg];
             // B operand from the raw taps, in place (waits for this column group's requests, issued an item ago)
-            if constexpr (!(VAR & 2)) {                                             // (VAR bits 2..16: developer ablations, timing only)
             if (c3) X[12] = 0.f;                                                    // tap 4 * 12 + 3 = 51 does not exist
 #pragma unroll
             for (int m = 16; m >= 0; --m) {
@@ -1822,7 +1690,6 @@ __global__ __launch_bounds__(WAVES * 64, 2) void sepconv_gray16_mfma(
             for (int m = 16; m >= 0; --m) X[m] = s2 ? (m >= 2 ? X[m - 2] : 0.f) : X[m];
 #pragma unroll
             for (int m = 16; m >= 0; --m) X[m] = s4 ? (m >= 4 ? X[m - 4] : 0.f) : X[m];
-            }
 
             f32x4 acc[3], accr = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -1831,12 +1698,9 @@ __global__ __launch_bounds__(WAVES * 64, 2) void sepconv_gray16_mfma(
             for (int m = 0; m < 17; ++m) {
                 const int col = 16 * cg + 4 * m;
 #pragma unroll
-                for (int T = 0; T < 3; ++T) {
-                    if constexpr (VAR & 8) acc[T][m & 3] += abig[16 * T * RS + col] * X[m];
-                    else acc[T] = __builtin_amdgcn_mfma_f32_16x16x4f32(abig[16 * T * RS + col], X[m], acc[T], 0, 0, 0);
-                }
-                if constexpr (VAR & 8) accr[m & 3] += arem[col] * X[m];
-                else accr = __builtin_amdgcn_mfma_f32_4x4x1f32(arem[col], X[m], accr, 0, 0, 0);
+                for (int T = 0; T < 3; ++T)
+                    acc[T] = __builtin_amdgcn_mfma_f32_16x16x4f32(abig[16 * T * RS + col], X[m], acc[T], 0, 0, 0);
+                accr = __builtin_amdgcn_mfma_f32_4x4x1f32(arem[col], X[m], accr, 0, 0, 0);
             }
             float o = 0.f;
 #pragma unroll
@@ -1845,14 +1709,10 @@ __global__ __launch_bounds__(WAVES * 64, 2) void sepconv_gray16_mfma(
                 for (int r = 0; r < 4; ++r) o = fmaf(Vv[cg][4 * T + r], acc[T][r], o);
 #pragma unroll
             for (int r = 0; r < 3; ++r) o = fmaf(Vv[cg][12 + r], accr[r], o);
-            if constexpr (!(VAR & 16)) {
-                o += __shfl_xor(o, 16);
-                o += __shfl_xor(o, 32);
-            }
+            o += __shfl_xor(o, 16);
+            o += __shfl_xor(o, 32);
             res = (kq == cg) ? o : res;
-            if constexpr (VAR & 4) { }
-            else if constexpr (VAR & 1) { if (more) request(cg, 1, rhn, rvn, nextoff); }     // every column group as soon as it is done
-            else if ((cg & 1) && more) request(cg - 1, 2, rhn, rvn, nextoff);              // wave-uniform: this pair's registers, for my next item
+            if ((cg & 1) && more) request(cg - 1, 2, rhn, rvn, nextoff);              // wave-uniform: this pair's registers, for my next item
         }
         const float csum = (res + res) + res;
         if (img == 0) first = csum;
@@ -2325,11 +2185,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_gradv_mfma(
     load_taps_buf<BF>(hs, rh, (uint32_t)(yfirst * W + x0) * 4u, plane4, xoff);
 
     // round 4: the tile by LDS-DMA, as in the forward kernel (one memory latency per tile instead of dependent register batches)
-#if SSTEM_GRAY_DMA
     stage_gray_tile_dma<WAVES * 64, ROWS, RS, false>(lds, in + (b * 3) * Hin * Win, (int)Hin, (int)Win, (int)y0, (int)x0);
-#else
-    stage_gray_tile<WAVES * 64, ROWS, RS, false>(lds, in + (b * 3) * Hin * Win, (int)Hin, (int)Win, (int)y0, (int)x0);
-#endif
     __syncthreads();
 
     auto do_row = [&](float (&hc)[KSTEPS], float (&hx)[PFH ? KSTEPS : 1], const int rr, const bool more) __attribute__((always_inline)) {
@@ -2461,8 +2317,10 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_gradv_mfma(
 // ds_read_b128 of 64 consecutive columns (same 4-row chunk) is conflict-free.
 constexpr int TCOLS = 120;   // 64 + 50 halo, + t-tiles reach col 4*13+3+63 = 118
 constexpr int KSTEPS_T = 56; // 14 aligned 4-row chunks cover 51 taps at any row phase
+// LDS bytes of the column-major image of a tile of tr output rows (ROWS = tr + 51 + 4 and PITCH_T of the kernels below), ch channels
+constexpr size_t cm_lds_bytes(int ch, int tr) { return (size_t)ch * TCOLS * (((tr + F + 4 + 3) / 4 * 4) | 4) * sizeof(float); }
 
-template <int CH, int WAVES, int RPW, bool COALESCE>
+template <int CH, int WAVES, int RPW>
 __global__ __launch_bounds__(WAVES * 64) void sepconv_gradh_mfma(
     const float* __restrict__ in, const float* __restrict__ g, const float* __restrict__ ver,
     float* __restrict__ gh, TileArgs args, const int* __restrict__ gray_flag)
@@ -2549,7 +2407,7 @@ __global__ __launch_bounds__(WAVES * 64) void sepconv_gradh_mfma(
         for (int c = 0; c < CH; ++c) a_cur[c] = *reinterpret_cast<const f32x4*>(abase + c * CSTRIDE);
 
         const int ntt = (args.dbg & 4) ? 1 : 14;
-        float carry[3] = {0.f, 0.f, 0.f};    // COALESCE: entries t = 4tt-3 .. 4tt-1 of the previous tile
+        float carry[3] = {0.f, 0.f, 0.f};    // entries t = 4tt-3 .. 4tt-1 of the previous tile
 #pragma unroll 1
         for (int tt = 0; tt < ntt; ++tt) {
             f32x4 acc[CH];
@@ -2580,47 +2438,31 @@ __global__ __launch_bounds__(WAVES * 64) void sepconv_gradh_mfma(
                 for (int c = 0; c < CH; ++c) a_cur[c] = a_nxt[c];
             }
             // acc[c][i] = G_c[t = 4tt+i ; my pixel j=sub];  gH[fx = t - j]
-            if constexpr (COALESCE) {
-                // Re-sort in registers so that every store is one whole 256-B row segment of ONE tap plane (measured on
-                // the gray kernel: four-plane 64-B pieces cost 20-25 %): plane f takes entry t = f + j, a 4-way select
-                // over a window of this tile's four entries and the last three of the previous tile.  Same values.
-                float w[7];
+            // Re-sort in registers so that every store is one whole 256-B row segment of ONE tap plane (measured on
+            // the gray kernel: four-plane 64-B pieces cost 20-25 %): plane f takes entry t = f + j, a 4-way select
+            // over a window of this tile's four entries and the last three of the previous tile.  Same values.
+            float w[7];
 #pragma unroll
-                for (int u = 0; u < 3; ++u) w[u] = carry[u];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float sc = 0.f;
-#pragma unroll
-                    for (int c = 0; c < CH; ++c) sc = fmaf(gch[c], acc[c][i], sc);
-                    w[3 + i] = sc;
-                }
-#pragma unroll
-                for (int u = 0; u < 3; ++u) carry[u] = w[4 + u];
-                if (xok) {
-                    const bool m1 = sub >= 1, m2 = sub >= 2, m3 = sub == 3;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int f = tt * 4 - 3 + q;                    // wave-uniform
-                        if (f >= 0 && f < F) {
-                            const float val = m3 ? w[q + 3] : (m2 ? w[q + 2] : (m1 ? w[q + 1] : w[q]));
-                            gfloat* dst = stg_ptr(gh + ((b * F + f) * H + y) * W + x0, xoff);
-                            if (args.c0 == 0) *dst = val; else *dst += val;
-                        }
-                    }
-                }
-            } else
+            for (int u = 0; u < 3; ++u) w[u] = carry[u];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int fx = tt * 4 + i - sub;
-                float s = 0.f;
+                float sc = 0.f;
 #pragma unroll
-                for (int c = 0; c < CH; ++c) s = fmaf(gch[c], acc[c][i], s);
-                if (xok && fx >= 0 && fx < F) {
-                    // plane fx = 4tt+i-sub is lane-dependent: uniform base of plane (4tt+i-3) + per-lane
-                    // ((3-sub)*plane + lane)*4
-                    gfloat* dst = stg_ptr(gh + ((b * F + (tt * 4 + i - 3)) * H + y) * W + x0,
-                                         (uint32_t)((3 - sub) * plane) * 4u + xoff);
-                    if (args.c0 == 0) *dst = s; else *dst += s;
+                for (int c = 0; c < CH; ++c) sc = fmaf(gch[c], acc[c][i], sc);
+                w[3 + i] = sc;
+            }
+#pragma unroll
+            for (int u = 0; u < 3; ++u) carry[u] = w[4 + u];
+            if (xok) {
+                const bool m1 = sub >= 1, m2 = sub >= 2, m3 = sub == 3;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int f = tt * 4 - 3 + q;                    // wave-uniform
+                    if (f >= 0 && f < F) {
+                        const float val = m3 ? w[q + 3] : (m2 ? w[q + 2] : (m1 ? w[q + 1] : w[q]));
+                        gfloat* dst = stg_ptr(gh + ((b * F + f) * H + y) * W + x0, xoff);
+                        if (args.c0 == 0) *dst = val; else *dst += val;
+                    }
                 }
             }
         }
@@ -3143,8 +2985,8 @@ hipError_t launch_bwd_direct(const float* g, const float* in, const float* ver, 
     return hipGetLastError();
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize belongs to the (kernel, device) pair: `done` is the calling launcher
-// instantiation's own bit set of devices that already have it (one static per kernel instantiation).
+// hipFuncAttributeMaxDynamicSharedMemorySize belongs to the (kernel, device) pair: `done` is the caller's own bit set of
+// devices that already have it (launch_tiled keeps one per kernel instantiation).
 template <typename K>
 static hipError_t set_lds(K kernel, size_t bytes, std::atomic<uint64_t>& done)
 {
@@ -3158,114 +3000,43 @@ static hipError_t set_lds(K kernel, size_t bytes, std::atomic<uint64_t>& done)
     return e;
 }
 
-// Tile shapes: WAVES waves x RPW rows per wave.  0: 8x4, 1: 12x3, 2: 12x2, 3: 16x2 (default), 4: 16x3 -- the
-// developer knob SSTEM_TILE picks one for A/B runs.
-static int tile_variant()
+// Every tiled launch: kernel K (WAVES waves, tiles of 64 pixels x TR rows, LDS bytes of dynamic LDS) on one workgroup per tile of
+// `a`.  Last is the kernel's last argument: FusedArgs or the gray flag (const int*).
+template <auto K, int WAVES, int TR, size_t LDS, typename Last>
+static hipError_t launch_tiled(const float* p0, const float* p1, const float* p2, float* p3, TileArgs a, hipStream_t s, Last last)
 {
-    static const int cached = [] {
-        const char* e = getenv("SSTEM_TILE");
-        const int v = e ? atoi(e) : 3;   // default: 16 waves x 2 rows (fastest measured on MI355X)
-        return (v >= 0 && v <= 4) ? v : 3;
-    }();
-    return cached;
-}
-static int tile_rows(int variant) { return variant == 0 ? 32 : (variant == 1 ? 36 : (variant == 2 ? 24 : (variant == 3 ? 32 : 48))); }
-
-template <int MODE, int CH, int WAVES, int RPW>
-static hipError_t launch_rowmajor_v(const float* in, const float* vg, const float* hor, float* out,
-                                    const TileArgs& a, hipStream_t s,
-                                    FusedArgs fa = FusedArgs{nullptr, nullptr, nullptr, nullptr})
-{
-    constexpr int TR = WAVES * RPW;
-    constexpr int CHL = CH;
-    constexpr size_t lds_bytes = (size_t)CHL * (TR + F) * rm_pitch_tile(CHL, WAVES, RPW) * sizeof(float);
-    static_assert(lds_bytes <= 160 * 1024, "LDS");
-    auto k = sepconv_rowmajor_mfma<MODE, CH, WAVES, RPW>;
-    static std::atomic<uint64_t> lds_set{0};                // per instantiation: devices whose attribute is set
-    const hipError_t attr = set_lds(k, lds_bytes, lds_set);
-    if (attr != hipSuccess) return attr;
-    const int64_t nwg = a.B * a.tiles_y * a.tiles_x;
-    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(WAVES * 64), lds_bytes, s, in, vg, hor, out, a, fa);
-    return hipGetLastError();
-}
-
-template <int MODE, int CH>
-static hipError_t launch_rowmajor(const float* in, const float* vg, const float* hor, float* out,
-                                  const TileArgs& a, hipStream_t s)
-{
-    switch (tile_variant()) {
-        case 1: return launch_rowmajor_v<MODE, CH, 12, 3>(in, vg, hor, out, a, s);
-        case 2: return launch_rowmajor_v<MODE, CH, 12, 2>(in, vg, hor, out, a, s);
-        case 3: return launch_rowmajor_v<MODE, CH, 16, 2>(in, vg, hor, out, a, s);
-        case 4: return launch_rowmajor_v<MODE, CH, 16, 3>(in, vg, hor, out, a, s);
-        default: return launch_rowmajor_v<MODE, CH, 8, 4>(in, vg, hor, out, a, s);
-    }
-}
-
-// SSTEM_GH_COALESCE=0 keeps the four-plane store pieces (A/B runs); default: results re-sorted into whole-row stores
-static bool gradh_coalesce()
-{
-    static const bool on = [] { const char* e = getenv("SSTEM_GH_COALESCE"); return !(e && atoi(e) == 0); }();
-    return on;
-}
-
-template <int CH, int WAVES, int RPW, bool COALESCE>
-static hipError_t launch_gradh_vc(const float* in, const float* g, const float* ver, float* gh,
-                                  const TileArgs& a, hipStream_t s, const int* flag)
-{
-    constexpr int TR = WAVES * RPW;
-    constexpr int ROWS = TR + F + 4;
-    constexpr int PITCH_T = ((ROWS + 3) / 4 * 4) | 4;
-    constexpr size_t lds_bytes = (size_t)CH * TCOLS * PITCH_T * sizeof(float);
-    static_assert(lds_bytes <= 160 * 1024, "LDS");
-    auto k = sepconv_gradh_mfma<CH, WAVES, RPW, COALESCE>;
-    static std::atomic<uint64_t> lds_set{0};
-    const hipError_t attr = set_lds(k, lds_bytes, lds_set);
-    if (attr != hipSuccess) return attr;
-    const int64_t nwg = a.B * a.tiles_y * a.tiles_x;
-    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(WAVES * 64), lds_bytes, s, in, g, ver, gh, a, flag);
-    return hipGetLastError();
-}
-
-template <int CH, int WAVES, int RPW>
-static hipError_t launch_gradh_v(const float* in, const float* g, const float* ver, float* gh,
-                                 const TileArgs& a, hipStream_t s, const int* flag = nullptr)
-{
-    return gradh_coalesce() ? launch_gradh_vc<CH, WAVES, RPW, true>(in, g, ver, gh, a, s, flag)
-                            : launch_gradh_vc<CH, WAVES, RPW, false>(in, g, ver, gh, a, s, flag);
-}
-
-// three independent channels: the streaming form (8 waves x 4 rows, 2 waves per SIMD) under the same switch and limits as the forward's
-static hipError_t launch_rgb_gradh_stream(const float* in, const float* g, const float* ver, float* gh, TileArgs a, hipStream_t s,
-                                          const int* flag)
-{
-    constexpr int WAVES = 8, RPW = 4, TR = WAVES * RPW;
-    constexpr int ROWS = TR + F + 4;
-    constexpr int PITCH_T = ((ROWS + 3) / 4 * 4) | 4;
-    constexpr size_t lds_bytes = (size_t)3 * TCOLS * PITCH_T * sizeof(float);
-    static_assert(lds_bytes <= 160 * 1024, "LDS");
-    auto k = sepconv_rgb_gradh_stream_mfma<WAVES, RPW>;
-    static std::atomic<uint64_t> lds_set{0};
-    const hipError_t attr = set_lds(k, lds_bytes, lds_set);
+    static_assert(LDS <= 160 * 1024, "LDS");
+    static std::atomic<uint64_t> lds_set{0};                // per kernel instantiation: devices whose attribute is set
+    const hipError_t attr = set_lds(K, LDS, lds_set);
     if (attr != hipSuccess) return attr;
     a.tiles_y = (a.H + TR - 1) / TR;
     const int64_t nwg = a.B * a.tiles_y * a.tiles_x;
     if (nwg <= 0 || nwg > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(WAVES * 64), lds_bytes, s, in, g, ver, gh, a, flag);
+    hipLaunchKernelGGL(K, dim3((unsigned)nwg), dim3(WAVES * 64), LDS, s, p0, p1, p2, p3, a, last);
     return hipGetLastError();
 }
 
-template <int CH>
-static hipError_t launch_gradh(const float* in, const float* g, const float* ver, float* gh,
-                               const TileArgs& a, hipStream_t s)
+// The round-1 generic kernels.  16 waves x 2 rows is the fastest shape measured on MI355X for the forward and the gradients; the fused
+// apply (MODE 2) runs 8 waves x 4 rows (next-row coefficient prefetch, 256-register budget: 2.06 against 2.35 ms on grayscale frames).
+template <int MODE, int CH, int WAVES = 16, int RPW = 2>
+static hipError_t launch_rowmajor(const float* in, const float* vg, const float* hor, float* out, const TileArgs& a, hipStream_t s,
+                                  const FusedArgs& fa = FusedArgs{nullptr, nullptr, nullptr, nullptr})
 {
-    switch (tile_variant()) {
-        case 1: return launch_gradh_v<CH, 12, 3>(in, g, ver, gh, a, s);
-        case 2: return launch_gradh_v<CH, 12, 2>(in, g, ver, gh, a, s);
-        case 3: return launch_gradh_v<CH, 16, 2>(in, g, ver, gh, a, s);
-        case 4: return launch_gradh_v<CH, 16, 3>(in, g, ver, gh, a, s);
-        default: return launch_gradh_v<CH, 8, 4>(in, g, ver, gh, a, s);
-    }
+    return launch_tiled<sepconv_rowmajor_mfma<MODE, CH, WAVES, RPW>, WAVES, WAVES * RPW, rm_lds_bytes(CH, WAVES * RPW)>(in, vg, hor, out, a, s, fa);
+}
+
+template <int CH>
+static hipError_t launch_gradh(const float* in, const float* g, const float* ver, float* gh, const TileArgs& a, hipStream_t s,
+                               const int* flag = nullptr)
+{
+    return launch_tiled<sepconv_gradh_mfma<CH, 16, 2>, 16, 32, cm_lds_bytes(CH, 32)>(in, g, ver, gh, a, s, flag);
+}
+
+// three independent channels: the streaming form (8 waves x 4 rows, 2 waves per SIMD) under the same switch and limits as the forward's
+static hipError_t launch_rgb_gradh_stream(const float* in, const float* g, const float* ver, float* gh, const TileArgs& a, hipStream_t s,
+                                          const int* flag)
+{
+    return launch_tiled<sepconv_rgb_gradh_stream_mfma<8, 4>, 8, 32, cm_lds_bytes(3, 32)>(in, g, ver, gh, a, s, flag);
 }
 
 static TileArgs make_args(int64_t B, int64_t C, int64_t H, int64_t W)
@@ -3273,8 +3044,7 @@ static TileArgs make_args(int64_t B, int64_t C, int64_t H, int64_t W)
     TileArgs a;
     a.B = B; a.C = C; a.H = H; a.W = W;
     a.tiles_x = (W + 63) / 64;
-    const int tr = tile_rows(tile_variant());
-    a.tiles_y = (H + tr - 1) / tr;
+    a.tiles_y = (H + 31) / 32;                      // 32-row tiles; launch_tiled sets it for the kernel's own tile height
     a.c0 = 0;
     a.in_planes = 3;
     static const int dbg = [] { const char* d = getenv("SSTEM_DEBUG_FLAGS"); return d ? atoi(d) : 0; }();
@@ -3295,21 +3065,11 @@ bool mfma_grid_ok(int64_t B, int64_t H, int64_t W)
 //   2: 4 waves x 16 rows, otherwise as 1      3: as 2 with a 2-deep A ring
 //   6 / 7 / 8: 2 x 8, 4 x 4, 2 x 4 rows at 3 waves per SIMD (small grids; 7 is the default below 512 workgroups)
 template <int MODE, int WAVES, int RPW, int WPE, bool PFH, int RING, bool BLK = false, bool BF = false>
-static hipError_t launch_gray_v(const float* in, const float* ver, const float* hor, float* out, TileArgs a,
+static hipError_t launch_gray_v(const float* in, const float* ver, const float* hor, float* out, const TileArgs& a,
                                 hipStream_t s, const FusedArgs& fa)
 {
-    constexpr int TR = WAVES * RPW;
-    constexpr size_t lds_bytes = (size_t)(TR + F) * rm_pitch(1) * sizeof(float);
-    static_assert(lds_bytes <= 160 * 1024, "LDS");
-    auto k = sepconv_gray_mfma<MODE, WAVES, RPW, WPE, PFH, RING, BLK, BF>;
-    static std::atomic<uint64_t> lds_set{0};
-    const hipError_t attr = set_lds(k, lds_bytes, lds_set);
-    if (attr != hipSuccess) return attr;
-    a.tiles_y = (a.H + TR - 1) / TR;
-    const int64_t nwg = a.B * a.tiles_y * a.tiles_x;
-    if (nwg <= 0 || nwg > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(WAVES * 64), lds_bytes, s, in, ver, hor, out, a, fa);
-    return hipGetLastError();
+    return launch_tiled<sepconv_gray_mfma<MODE, WAVES, RPW, WPE, PFH, RING, BLK, BF>, WAVES, WAVES * RPW, rm_lds_bytes(1, WAVES * RPW)>(
+        in, ver, hor, out, a, s, fa);
 }
 
 // Row-pair forms of the blocked fused apply (4 waves x 16 rows, 2 waves per SIMD): sepconv_gray_mfma_pair (group by group) and
@@ -3326,25 +3086,18 @@ static int gray_pair_variant()
 }
 
 template <int WAVES, int RPW, int WPE, bool HP = false>
-static hipError_t launch_gray_pair_v(const float* in, const float* ver, const float* hor, float* out, TileArgs a,
+static hipError_t launch_gray_pair_v(const float* in, const float* ver, const float* hor, float* out, const TileArgs& a,
                                      hipStream_t s, const FusedArgs& fa)
 {
     constexpr int TR = WAVES * RPW;
-    constexpr size_t lds_bytes = (size_t)(TR + F) * rm_pitch(1) * sizeof(float);
+    constexpr size_t lds_bytes = rm_lds_bytes(1, TR);
     static_assert(lds_bytes * WPE <= 160 * 1024, "LDS");
-    auto k = HP ? sepconv_gray_mfma_pair_hp<WAVES, RPW, WPE> : sepconv_gray_mfma_pair<WAVES, RPW, WPE>;
-    static std::atomic<uint64_t> lds_set{0};
-    const hipError_t attr = set_lds(k, lds_bytes, lds_set);
-    if (attr != hipSuccess) return attr;
-    a.tiles_y = (a.H + TR - 1) / TR;
-    const int64_t nwg = a.B * a.tiles_y * a.tiles_x;
-    if (nwg <= 0 || nwg > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(WAVES * 64), lds_bytes, s, in, ver, hor, out, a, fa);
-    return hipGetLastError();
+    if constexpr (HP) return launch_tiled<sepconv_gray_mfma_pair_hp<WAVES, RPW, WPE>, WAVES, TR, lds_bytes>(in, ver, hor, out, a, s, fa);
+    else return launch_tiled<sepconv_gray_mfma_pair<WAVES, RPW, WPE>, WAVES, TR, lds_bytes>(in, ver, hor, out, a, s, fa);
 }
 
 template <int MODE, bool BLK = false>
-static hipError_t launch_gray(const float* in, const float* vg, const float* hor, float* out, TileArgs a,
+static hipError_t launch_gray(const float* in, const float* vg, const float* hor, float* out, const TileArgs& a,
                               hipStream_t s, const FusedArgs& fa)
 {
     static const int forced = [] { const char* e = getenv("SSTEM_GRAY_SHAPE"); return e ? atoi(e) : -1; }();
@@ -3398,21 +3151,10 @@ static bool rgb_stream_enabled(int64_t H, int64_t W)
 }
 
 template <int MODE>
-static hipError_t launch_rgb_stream(const float* in, const float* ver, const float* hor, float* out, TileArgs a, hipStream_t s,
+static hipError_t launch_rgb_stream(const float* in, const float* ver, const float* hor, float* out, const TileArgs& a, hipStream_t s,
                                     const FusedArgs& fa)
 {
-    constexpr int WAVES = 8, RPW = 4, TR = WAVES * RPW;
-    constexpr size_t lds_bytes = (size_t)(TR + F) * 3 * rm_pitch(3) * sizeof(float);
-    static_assert(lds_bytes <= 160 * 1024, "LDS");
-    auto k = sepconv_rgb_stream_mfma<MODE, WAVES, RPW>;
-    static std::atomic<uint64_t> lds_set{0};
-    const hipError_t attr = set_lds(k, lds_bytes, lds_set);
-    if (attr != hipSuccess) return attr;
-    a.tiles_y = (a.H + TR - 1) / TR;
-    const int64_t nwg = a.B * a.tiles_y * a.tiles_x;
-    if (nwg <= 0 || nwg > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(WAVES * 64), lds_bytes, s, in, ver, hor, out, a, fa);
-    return hipGetLastError();
+    return launch_tiled<sepconv_rgb_stream_mfma<MODE, 8, 4>, 8, 32, rm_lds_bytes(3, 32)>(in, ver, hor, out, a, s, fa);
 }
 
 // SSTEM_GRAY_KERNEL=0 disables the trusted-gray build + device dispatch (A/B runs); the in-kernel per-tile vote stays.
@@ -3429,7 +3171,7 @@ hipError_t launch_fwd_mfma(const float* in, const float* ver, const float* hor, 
     TileArgs a = make_args(B, C, H, W);
     hipError_t e = hipSuccess;
     int* flag = nullptr;
-    if (C == 3 && gray_dispatch_enabled(H, W) && tile_rows(tile_variant()) == 32) {
+    if (C == 3 && gray_dispatch_enabled(H, W)) {
         flag = next_gray_flag(s, e);          // nullptr without an error: no free slot, the generic build serves the call
         if (e != hipSuccess) return e;
     }
@@ -3439,10 +3181,7 @@ hipError_t launch_fwd_mfma(const float* in, const float* ver, const float* hor, 
         if (e != hipSuccess) return e;
         const FusedArgs fa{nullptr, nullptr, nullptr, flag};
         if (rgb_stream_enabled(H, W)) e = launch_rgb_stream<0>(in, ver, hor, out, a, s, fa);
-        else switch (tile_variant()) {
-            case 0: e = launch_rowmajor_v<0, 3, 8, 4>(in, ver, hor, out, a, s, fa); break;
-            default: e = launch_rowmajor_v<0, 3, 16, 2>(in, ver, hor, out, a, s, fa); break;
-        }
+        else e = launch_rowmajor<0, 3>(in, ver, hor, out, a, s, fa);
         if (e != hipSuccess) return e;
         return launch_gray<0>(in, ver, hor, out, a, s, fa);
     }
@@ -3477,14 +3216,8 @@ hipError_t launch_interp_fused(const float* i1, const float* i2, const float* k1
             if (e != hipSuccess) return e;
         }
     }
-    // measured on MI355X: the 8-wave shape (next-row coefficient prefetch, 256-register budget) wins the fused
-    // launch on grayscale frames (2.06 vs 2.35 ms) and ties on independent channels; SSTEM_FUSED_TILE overrides
-    static const int fv = [] { const char* e = getenv("SSTEM_FUSED_TILE"); return e ? atoi(e) : 0; }();
-    if (fv == 0 && rgb_stream_enabled(H, W)) return launch_rgb_stream<2>(i2, k2v, k2h, out, a, s, fa);
-    if (fv == 1) { a.tiles_y = (H + 35) / 36; return launch_rowmajor_v<2, 3, 12, 3>(i2, k2v, k2h, out, a, s, fa); }
-    if (fv == 0) { a.tiles_y = (H + 31) / 32; return launch_rowmajor_v<2, 3, 8, 4>(i2, k2v, k2h, out, a, s, fa); }
-    a.tiles_y = (H + 31) / 32;
-    return launch_rowmajor_v<2, 3, 16, 2>(i2, k2v, k2h, out, a, s, fa);
+    if (rgb_stream_enabled(H, W)) return launch_rgb_stream<2>(i2, k2v, k2h, out, a, s, fa);
+    return launch_rowmajor<2, 3, 8, 4>(i2, k2v, k2h, out, a, s, fa);   // see rgb_stream_enabled
 }
 
 // The 16x16x4 formulation of the fused apply on grayscale planes (sepconv_gray16_mfma): OPT-IN (SSTEM_GRAY16=1, read at every call so
@@ -3499,38 +3232,20 @@ static int gray16_mode()          // 0: the 4x4x1 kernel; 1: four column groups 
 }
 static bool gray16_enabled() { const int m = gray16_mode(); return m >= 1 && m <= 3; }
 
-template <int WAVES, int RPW, bool BLK, int VAR = 0>
-static hipError_t launch_gray16_v(const float* in, const float* ver, const float* hor, float* out, TileArgs a, hipStream_t s, const FusedArgs& fa)
+template <int WAVES, int RPW, bool BLK>
+static hipError_t launch_gray16_v(const float* in, const float* ver, const float* hor, float* out, const TileArgs& a, hipStream_t s, const FusedArgs& fa)
 {
     constexpr int TR = WAVES * RPW;
-    constexpr size_t lds_bytes = (size_t)2 * (TR + F) * G16_RS * sizeof(float);
-    static_assert(lds_bytes <= 80 * 1024, "two workgroups per CU");
-    auto k = sepconv_gray16_mfma<WAVES, RPW, BLK, VAR>;
-    static std::atomic<uint64_t> lds_set{0};
-    const hipError_t attr = set_lds(k, lds_bytes, lds_set);
-    if (attr != hipSuccess) return attr;
-    a.tiles_y = (a.H + TR - 1) / TR;
-    const int64_t nwg = a.B * a.tiles_y * a.tiles_x;
-    if (nwg <= 0 || nwg > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(WAVES * 64), lds_bytes, s, in, ver, hor, out, a, fa);
-    return hipGetLastError();
+    static_assert(g16_lds_bytes(TR) <= 80 * 1024, "two workgroups per CU");
+    return launch_tiled<sepconv_gray16_mfma<WAVES, RPW, BLK>, WAVES, TR, g16_lds_bytes(TR)>(in, ver, hor, out, a, s, fa);
 }
 
 template <int RPW, bool BLK, bool SKEW_AHEAD = false>
-static hipError_t launch_gray16p_v(const float* in, const float* ver, const float* hor, float* out, TileArgs a, hipStream_t s, const FusedArgs& fa)
+static hipError_t launch_gray16p_v(const float* in, const float* ver, const float* hor, float* out, const TileArgs& a, hipStream_t s, const FusedArgs& fa)
 {
-    constexpr int TR = 2 * RPW;
-    constexpr size_t lds_bytes = (size_t)2 * (TR + F) * G16_RS * sizeof(float);
-    static_assert(lds_bytes <= 80 * 1024, "two workgroups per CU");
-    auto k = sepconv_gray16p_mfma<RPW, BLK, SKEW_AHEAD>;
-    static std::atomic<uint64_t> lds_set{0};
-    const hipError_t attr = set_lds(k, lds_bytes, lds_set);
-    if (attr != hipSuccess) return attr;
-    a.tiles_y = (a.H + TR - 1) / TR;
-    const int64_t nwg = a.B * a.tiles_y * a.tiles_x;
-    if (nwg <= 0 || nwg > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(256), lds_bytes, s, in, ver, hor, out, a, fa);
-    return hipGetLastError();
+    constexpr int TR = 2 * RPW;               // four waves: two row groups x two halves of the row segment
+    static_assert(g16_lds_bytes(TR) <= 80 * 1024, "two workgroups per CU");
+    return launch_tiled<sepconv_gray16p_mfma<RPW, BLK, SKEW_AHEAD>, 4, TR, g16_lds_bytes(TR)>(in, ver, hor, out, a, s, fa);
 }
 
 template <bool BLK>
@@ -3545,24 +3260,7 @@ static hipError_t launch_gray16(const float* in, const float* ver, const float* 
         return launch_gray16p_v<12, BLK>(in, ver, hor, out, a, s, fa);
     }
     // 24-row tiles (6 rows per wave); 16-row tiles when those give fewer than two workgroups per CU
-    static const int forced = [] { const char* e = getenv("SSTEM_GRAY16_ROWS"); return e ? atoi(e) : 0; }();
-    const bool small = forced ? forced == 16 : a.B * a.tiles_x * ((a.H + 23) / 24) < 512;
-    if (small) return launch_gray16_v<4, 4, BLK>(in, ver, hor, out, a, s, fa);
-#if SSTEM_GRAY16_ABLATE      // developer builds only (tools/build_ablate.sh x "-DSSTEM_GRAY16_ABLATE=1"): timing-only variants, wrong results above 1
-    static const int var = [] { const char* e = getenv("SSTEM_GRAY16_VAR"); return e ? atoi(e) : 0; }();
-    if constexpr (BLK) {
-        switch (var) {
-            case 1: return launch_gray16_v<4, 6, BLK, 1>(in, ver, hor, out, a, s, fa);
-            case 2: return launch_gray16_v<4, 6, BLK, 2>(in, ver, hor, out, a, s, fa);
-            case 4: return launch_gray16_v<4, 6, BLK, 4>(in, ver, hor, out, a, s, fa);
-            case 8: return launch_gray16_v<4, 6, BLK, 8>(in, ver, hor, out, a, s, fa);
-            case 16: return launch_gray16_v<4, 6, BLK, 16>(in, ver, hor, out, a, s, fa);
-            case 6: return launch_gray16_v<4, 6, BLK, 6>(in, ver, hor, out, a, s, fa);
-            case 22: return launch_gray16_v<4, 6, BLK, 22>(in, ver, hor, out, a, s, fa);
-            default: break;
-        }
-    }
-#endif
+    if (a.B * a.tiles_x * ((a.H + 23) / 24) < 512) return launch_gray16_v<4, 4, BLK>(in, ver, hor, out, a, s, fa);
     return launch_gray16_v<4, 6, BLK>(in, ver, hor, out, a, s, fa);
 }
 
@@ -3636,21 +3334,11 @@ hipError_t launch_interp_fused_gray_blocked(const float* g1, const float* g2, co
 // Trusted-gray gradVertical launch; SSTEM_GRAY_GV_SHAPE: 0 = 4 waves x 8 rows (3 waves/SIMD), 1 = 4 x 16 with the
 // B-operand prefetch (2 waves/SIMD); default as launch_gray.
 template <int WAVES, int RPW, int WPE, bool PFH, int RING, bool BF = false>
-static hipError_t launch_gray_gradv_v(const float* in, const float* g, const float* hor, float* gv, TileArgs a,
+static hipError_t launch_gray_gradv_v(const float* in, const float* g, const float* hor, float* gv, const TileArgs& a,
                                       hipStream_t s, const int* flag)
 {
-    constexpr int TR = WAVES * RPW;
-    constexpr size_t lds_bytes = (size_t)(TR + F) * rm_pitch(1) * sizeof(float);
-    static_assert(lds_bytes <= 160 * 1024, "LDS");
-    auto k = sepconv_gray_gradv_mfma<WAVES, RPW, WPE, PFH, RING, BF>;
-    static std::atomic<uint64_t> lds_set{0};
-    const hipError_t attr = set_lds(k, lds_bytes, lds_set);
-    if (attr != hipSuccess) return attr;
-    a.tiles_y = (a.H + TR - 1) / TR;
-    const int64_t nwg = a.B * a.tiles_y * a.tiles_x;
-    if (nwg <= 0 || nwg > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(WAVES * 64), lds_bytes, s, in, g, hor, gv, a, flag);
-    return hipGetLastError();
+    return launch_tiled<sepconv_gray_gradv_mfma<WAVES, RPW, WPE, PFH, RING, BF>, WAVES, WAVES * RPW, rm_lds_bytes(1, WAVES * RPW)>(
+        in, g, hor, gv, a, s, flag);
 }
 
 static hipError_t launch_gray_gradv(const float* in, const float* g, const float* hor, float* gv, const TileArgs& a,
@@ -3666,23 +3354,11 @@ static hipError_t launch_gray_gradv(const float* in, const float* g, const float
 // Trusted-gray gradHorizontal launch; SSTEM_GRAY_GH_SHAPE: 0 = 4 waves x 8 rows (3 waves/SIMD), 1 = 4 x 16 with the
 // B-operand prefetch (2 waves/SIMD); 2, 3 = the same two with the results re-sorted in registers into whole-row stores.
 template <int WAVES, int RPW, int WPE, bool PFH, int RING, bool COALESCE, bool BF = false>
-static hipError_t launch_gray_gradh_v(const float* in, const float* g, const float* ver, float* gh, TileArgs a,
+static hipError_t launch_gray_gradh_v(const float* in, const float* g, const float* ver, float* gh, const TileArgs& a,
                                       hipStream_t s, const int* flag)
 {
-    constexpr int TR = WAVES * RPW;
-    constexpr int ROWS = TR + F + 4;
-    constexpr int PITCH_T = ((ROWS + 3) / 4 * 4) | 4;
-    constexpr size_t lds_bytes = (size_t)TCOLS * PITCH_T * sizeof(float);
-    static_assert(lds_bytes <= 160 * 1024, "LDS");
-    auto k = sepconv_gray_gradh_mfma<WAVES, RPW, WPE, PFH, RING, COALESCE, BF>;
-    static std::atomic<uint64_t> lds_set{0};
-    const hipError_t attr = set_lds(k, lds_bytes, lds_set);
-    if (attr != hipSuccess) return attr;
-    a.tiles_y = (a.H + TR - 1) / TR;
-    const int64_t nwg = a.B * a.tiles_y * a.tiles_x;
-    if (nwg <= 0 || nwg > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(WAVES * 64), lds_bytes, s, in, g, ver, gh, a, flag);
-    return hipGetLastError();
+    return launch_tiled<sepconv_gray_gradh_mfma<WAVES, RPW, WPE, PFH, RING, COALESCE, BF>, WAVES, WAVES * RPW, cm_lds_bytes(1, WAVES * RPW)>(
+        in, g, ver, gh, a, s, flag);
 }
 
 static hipError_t launch_gray_gradh(const float* in, const float* g, const float* ver, float* gh, const TileArgs& a,
@@ -3709,7 +3385,7 @@ hipError_t launch_bwd_mfma(const float* g, const float* in, const float* ver, co
     TileArgs a = make_args(B, C, H, W);
     hipError_t e = hipSuccess;
     int* flag = nullptr;
-    if (C == 3 && gray_dispatch_enabled(H, W) && tile_rows(tile_variant()) == 32) {
+    if (C == 3 && gray_dispatch_enabled(H, W)) {
         flag = next_gray_flag(s, e);
         if (e != hipSuccess) return e;
     }
@@ -3719,15 +3395,13 @@ hipError_t launch_bwd_mfma(const float* g, const float* in, const float* ver, co
         if (e != hipSuccess) return e;
         const FusedArgs fa{nullptr, nullptr, nullptr, flag};
         if (rgb_stream_enabled(H, W)) e = launch_rgb_stream<1>(in, g, hor, gv, a, s, fa);       // round 4: the streaming kernel's gradVertical
-        else if (tile_variant() == 0) e = launch_rowmajor_v<1, 3, 8, 4>(in, g, hor, gv, a, s, fa);
-        else e = launch_rowmajor_v<1, 3, 16, 2>(in, g, hor, gv, a, s, fa);
+        else e = launch_rowmajor<1, 3>(in, g, hor, gv, a, s, fa);
         if (e != hipSuccess) return e;
         e = launch_gray_gradv(in, g, hor, gv, a, s, flag);
         if (e != hipSuccess) return e;
         // gradHorizontal: same flag, same pair of launches
-        if (rgb_stream_enabled(H, W) && gradh_coalesce()) e = launch_rgb_gradh_stream(in, g, ver, gh, a, s, flag);       // round 4
-        else if (tile_variant() == 0) e = launch_gradh_v<3, 8, 4>(in, g, ver, gh, a, s, flag);
-        else e = launch_gradh_v<3, 16, 2>(in, g, ver, gh, a, s, flag);
+        if (rgb_stream_enabled(H, W)) e = launch_rgb_gradh_stream(in, g, ver, gh, a, s, flag);       // round 4
+        else e = launch_gradh<3>(in, g, ver, gh, a, s, flag);
         if (e != hipSuccess) return e;
         return launch_gray_gradh(in, g, ver, gh, a, s, flag);
     }
@@ -3736,7 +3410,7 @@ hipError_t launch_bwd_mfma(const float* g, const float* in, const float* ver, co
     else if (C == 2) e = launch_rowmajor<1, 2>(in, g, hor, gv, a, s);
     else e = launch_rowmajor<1, 1>(in, g, hor, gv, a, s);
     if (e != hipSuccess) return e;
-    if (C == 3 && rgb_stream_enabled(H, W) && gradh_coalesce()) e = launch_rgb_gradh_stream(in, g, ver, gh, a, s, nullptr);
+    if (C == 3 && rgb_stream_enabled(H, W)) e = launch_rgb_gradh_stream(in, g, ver, gh, a, s, nullptr);
     else if (C == 3) e = launch_gradh<3>(in, g, ver, gh, a, s);
     else if (C == 2) e = launch_gradh<2>(in, g, ver, gh, a, s);
     else e = launch_gradh<1>(in, g, ver, gh, a, s);
@@ -3749,7 +3423,7 @@ hipError_t launch_bwd_mfma(const float* g, const float* in, const float* ver, co
 // the direct kernels (one lane per element: correct for any C, slow -- the streaming three-channel kernels have no bf16 instance).
 static bool gray_bf16_ok(int64_t C, int64_t H, int64_t W)
 {
-    return C == 3 && gray_dispatch_enabled(H, W) && tile_rows(tile_variant()) == 32;
+    return C == 3 && gray_dispatch_enabled(H, W);
 }
 
 hipError_t launch_fwd_bf16coef(const float* in, const uint16_t* ver, const uint16_t* hor, float* out,

@@ -54,7 +54,7 @@ def timeit(fn, n):
     return e0.elapsed_time(e1) / n
 
 
-tag = "%s tile=%s dbg=%s" % ("gray" if a.gray else "rgb",os.environ.get("SSTEM_TILE", "default"), os.environ.get("SSTEM_DEBUG_FLAGS", "0"))
+tag = "%s dbg=%s" % ("gray" if a.gray else "rgb", os.environ.get("SSTEM_DEBUG_FLAGS", "0"))
 if "fwd" in a.what:
     ms = timeit(lambda: cunnex.SeparableConvolution_cuda_forward(inp, ver, hor, out), a.iters)
     by = lib.sstem_sepconv_forward_bytes(B, 3, S, S)

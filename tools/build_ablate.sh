@@ -1,7 +1,7 @@
 #!/bin/bash
 # Developer tool: builds variants of the native library for A/B runs into build_ablate/libsstem_<name>.so
-#   tools/build_ablate.sh <name> "<extra hipcc flags>"   e.g.  tools/build_ablate.sh mem "-DSSTEM_ABLATE=12"
-# (SSTEM_ABLATE bit mask and the other switches: top of sepconv_kernels.hip).  Select one at run time with
+#   tools/build_ablate.sh <name> "<extra hipcc flags>"   e.g.  tools/build_ablate.sh hpf6 "-DSSTEM_HPF=6"
+# (the build switches: top of sepconv_kernels.hip).  Select one at run time with
 # SSTEM_NATIVE_LIB=<path>.  The other objects come from the product build (run make first).
 set -e
 cd "$(dirname "$0")/../sstem-restoration_amd/csrc"
