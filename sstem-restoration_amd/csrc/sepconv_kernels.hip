@@ -49,8 +49,8 @@
 #endif
 #ifndef SSTEM_HP_T0       // multi-pass row-pair fused apply (sepconv_gray_mfma_pair_hp): A tiles of passes 0, 1 and 2 (set all three); if they
 #define SSTEM_HP_T0 4     // leave any of the 14, a fourth pass takes the rest.  The B-operand refills are spread over the last pass, so it
-#define SSTEM_HP_T1 4     // should be the longest the registers allow: 4 + 4 + 6 in three passes spills (profiles/r07), hence 4 + 4 + 2 + 4
-#define SSTEM_HP_T2 2
+#define SSTEM_HP_T1 4     // should be the longest the registers allow: 4 + 4 + 6 in three passes (236 VGPRs, no scratch, since pass 0's skew
+#define SSTEM_HP_T2 6     // takes two selects per tap: profiles/r08; with three it spilled, hence 4 + 4 + 2 + 4 in profiles/r07)
 #endif
 #ifndef SSTEM_HP_VEARLY
 #define SSTEM_HP_VEARLY 16 // the same kernel: at most so many slots of the vertical set that a pass leaves free take the next pass's first taps already
@@ -767,20 +767,24 @@ __device__ __forceinline__ void load_taps_buf(float (&dst)[KSTEPS], rsrc_t r, ui
 }
 
 // B operand of the banded 4x4x1 formulation from the raw taps, in place: h[t] <- H[t - j] for the lane's position
-// j = sub in its 4-pixel block, 0 outside [0,51).  Top-down, so that h[t] is overwritten only after entries
-// t+1..t+3 (its other readers) are done.  Pure selects: the values, and hence the results, are bit-identical to
-// loading them skewed.  Lanes beyond the image edge carry whatever lane 0's address holds (finite coefficient
-// data): column j of a block only ever feeds pixel j's own accumulators, which are never stored.
+// j = sub in its 4-pixel block, 0 outside [0,51).  Two selects per entry: p[t] = (j & 1) ? raw[t - 1] : raw[t] is
+// entry t for j < 2 and entry t + 2 for j >= 2 (h[t] = p[t - 2]), so each p is selected once and used twice.
+// Top-down, so that h[t] is overwritten only after p[t + 1] (its last reader) is done; p[t] and p[t - 1] are
+// carried.  Pure selects: the values, and hence the results, are bit-identical to loading them skewed.  Lanes
+// beyond the image edge carry whatever lane 0's address holds (finite coefficient data): column j of a block
+// only ever feeds pixel j's own accumulators, which are never stored.
 __device__ __forceinline__ void skew_taps_in_place(float (&h)[KSTEPS], int sub)
 {
-    const bool m1 = sub >= 1, m2 = sub >= 2, m3 = sub == 3;
+    const bool odd = sub & 1, m2 = sub >= 2;
+    auto raw = [&](int t) __attribute__((always_inline)) -> float { return (t >= 0 && t < F) ? h[t] : 0.f; };
+    float p0 = odd ? raw(KSTEPS - 2) : raw(KSTEPS - 1);   // p[t]
+    float p1 = odd ? raw(KSTEPS - 3) : raw(KSTEPS - 2);   // p[t - 1]
 #pragma unroll
     for (int t = KSTEPS - 1; t >= 0; --t) {
-        const float a0 = (t < F) ? h[t] : 0.f;
-        const float a1 = (t - 1 >= 0 && t - 1 < F) ? h[t - 1] : 0.f;
-        const float a2 = (t - 2 >= 0 && t - 2 < F) ? h[t - 2] : 0.f;
-        const float a3 = (t - 3 >= 0 && t - 3 < F) ? h[t - 3] : 0.f;
-        h[t] = m3 ? a3 : (m2 ? a2 : (m1 ? a1 : a0));
+        const float q = odd ? raw(t - 3) : raw(t - 2);     // p[t - 2], from raw taps not yet overwritten
+        h[t] = m2 ? q : p0;
+        p0 = p1;
+        p1 = q;
     }
 }
 
@@ -1271,11 +1275,13 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma_pair(
 // ---- trusted-gray fused apply, row pairs in a few passes (blocked coefficients) -------------------------------------------------
 // The same work as sepconv_gray_mfma_pair -- per pair 196 ds_read_b128, each feeding row y's tile a and row y + 4's tile a - 1, and the
 // same k-ordered chains and fy-ascending vertical sums, hence the same bits -- in another order, chosen for the coefficient requests:
-//   * the 14 A tiles are split into HP_NP passes (SSTEM_HP_T0 / T1 / T2 / the rest: 4 + 4 + 2 + 4).  Inside a pass the k-chunk
+//   * the 14 A tiles are split into HP_NP passes (SSTEM_HP_T0 / T1 / T2 / the rest: 4 + 4 + 6).  Inside a pass the k-chunk
 //     q = 0..13 is the OUTER loop and the pass's tiles the inner one, two tiles (four independent chains, 16 MFMAs) per step, so all
 //     chains of the pass are alive at once;
-//   * both B operands stay resident.  Pass 0 applies the skew chunk by chunk, just before the chunk's MFMAs (three raw taps per row are
-//     carried in registers, the same selects on the same values as skew_taps_in_place); the last pass re-requests entries 4q..4q+3 of
+//   * both B operands stay resident.  Pass 0 applies the skew chunk by chunk, just before the chunk's MFMAs, with TWO selects per tap:
+//     lane position j = lane & 3 needs raw[t - j]; p[t] = (j & 1) ? raw[t - 1] : raw[t] serves entry t (j < 2) and entry t + 2
+//     (j >= 2: B[t] = p[t - 2]).  Three values per row are carried in registers (p[t - 2], p[t - 1], raw[t - 1]); the values selected
+//     are those of skew_taps_in_place (the same two selects, all entries at once): the same bits.  The last pass re-requests 4q..4q+3 of
 //     both rows for the next pair right after chunk q, their last reader: 8 loads per chunk, every entry most of a pair ahead of its use;
 //   * one ring of vertical-tap registers holds the taps of the current pass; they are requested a few per chunk over the pass's first
 //     chunks (the registers are dead since the previous pass's vertical stage) and combined at the pass's end.  Registers the previous
@@ -1283,8 +1289,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma_pair(
 //   * A operands through a 2-deep register ring of such steps that runs across chunk and pass boundaries;
 //   * the pair loop exists once per phase (SSTEM_HP_PHASE_CT): the first phase has no parked-sum load, no mean and no u8 store; the
 //     parked sums and the results go through buffer resources like the coefficients.
-// No request burst and no pair-start drain.  The only s_waitcnt vmcnt(0) in the pair loop is the one for the last vertical tap of
-// pass 1, which is the newest request the wave has at that point (issued ten chunks earlier): it drains nothing.
+// No request burst and no pair-start drain: with the 4 + 4 + 6 split neither pair loop holds an s_waitcnt vmcnt(0).
 constexpr int HP_NP = (SSTEM_HP_T0 + SSTEM_HP_T1 + SSTEM_HP_T2 < 14) ? 4 : 3;
 constexpr int hp_a0(int h)
 {
@@ -1362,7 +1367,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma_pair_hp(
     const int64_t img_elems = (int64_t)(img_bytes >> 2);
     const uint32_t seg_x = (uint32_t)tx * (uint32_t)(F * 256);
     auto rowoff = [&](int64_t y) __attribute__((always_inline)) -> uint32_t { return (uint32_t)clampy(y) * seg_row + seg_x; };
-    const bool m1 = sub >= 1, m2 = sub >= 2, m3 = sub == 3;
+    const bool odd = sub & 1, m2 = sub >= 2;
     const bool stamp = pair_stamp_on(wave);
     // the image's output plane(s) as buffer resources: scalar row offset + the lane's byte offset, like the coefficient streams (no
     // per-lane 64-bit addresses held across the pair, one kind of memory instruction in the loop)
@@ -1450,7 +1455,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma_pair_hp(
 #pragma unroll
             for (int d = 0; d < 2; ++d) ar[0][d] = *reinterpret_cast<const f32x4*>(arow + hp_read_off(d, RS));
             float oA = 0.f, oB = 0.f;
-            float cA0 = 0.f, cA1 = 0.f, cA2 = 0.f, cB0 = 0.f, cB1 = 0.f, cB2 = 0.f;   // raw taps t - 3, t - 2, t - 1
+            float cA0 = 0.f, cA1 = 0.f, cA2 = 0.f, cB0 = 0.f, cB1 = 0.f, cB2 = 0.f;   // p[t - 2], p[t - 1], raw tap t - 1 (see the skew below)
             static_for<0, HP_NP>([&](auto hc) __attribute__((always_inline)) {
                 constexpr int h = decltype(hc)::value;
                 constexpr int NT = hp_nt(h), A0 = hp_a0(h), VPC = hp_vpc(h), E = hp_vearly(h), CO = hp_vown_chunks(h), VB = hp_vbase(h);
@@ -1470,10 +1475,11 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void sepconv_gray_mfma_pair_hp(
                             const int t = 4 * q + e;
                             if (t < KSTEPS) {
                                 const float rA = (t < F) ? hA[t] : 0.f, rB = (t < F) ? hB[t] : 0.f;
-                                hA[t] = m3 ? cA0 : (m2 ? cA1 : (m1 ? cA2 : rA));
-                                hB[t] = m3 ? cB0 : (m2 ? cB1 : (m1 ? cB2 : rB));
-                                cA0 = cA1; cA1 = cA2; cA2 = rA;
-                                cB0 = cB1; cB1 = cB2; cB2 = rB;
+                                const float pA = odd ? cA2 : rA, pB = odd ? cB2 : rB;   // p[t]: also entry t + 2's operand
+                                hA[t] = m2 ? cA0 : pA;
+                                hB[t] = m2 ? cB0 : pB;
+                                cA0 = cA1; cA1 = pA; cA2 = rA;
+                                cB0 = cB1; cB1 = pB; cB2 = rB;
                             }
                         }
                         if constexpr (q == 0) pair_stamp<1>(stamp, ph, rr >> 1);
@@ -3073,7 +3079,7 @@ static hipError_t launch_gray_v(const float* in, const float* ver, const float* 
 }
 
 // Row-pair forms of the blocked fused apply (4 waves x 16 rows, 2 waves per SIMD): sepconv_gray_mfma_pair (group by group) and
-// sepconv_gray_mfma_pair_hp (the same pair in four passes with the k-chunk as the outer loop: no request burst).
+// sepconv_gray_mfma_pair_hp (the same pair in three passes with the k-chunk as the outer loop: no request burst).
 // Developer knob SSTEM_GRAY_PAIR, read once, at the first trusted-gray launch of any kind: 0 = always the one-row kernel, 1 = the
 // multi-pass pair form when its grid gives every CU at least two workgroups (default), 2 = always the group-by-group pair form, 3 =
 // always the multi-pass pair form (A/B runs, tests).  At C2, same box, alternating: 1.2920 ms (group by group) against 1.2653

@@ -3,7 +3,7 @@
 
     tools/build_ablate.sh stamp "-DSSTEM_PAIR_STAMP=1"
     SSTEM_NATIVE_LIB=build_ablate/libsstem_stamp.so SSTEM_GRAY_PAIR=2 python tools/pair_stamps.py            # sepconv_gray_mfma_pair
-    SSTEM_NATIVE_LIB=build_ablate/libsstem_stamp.so SSTEM_GRAY_PAIR=3 python tools/pair_stamps.py 378,648,378  # ..._pair_hp, 4+4+2+4
+    SSTEM_NATIVE_LIB=build_ablate/libsstem_stamp.so SSTEM_GRAY_PAIR=3 python tools/pair_stamps.py 378,432,594  # ..._pair_hp, 4+4+6
 
 Wave 0 of every workgroup writes s_memtime at five points of each pair: 0 pair start, 1 first MFMA (the waits for the B operand and
 its skew are over), 2 and 3 two marks inside the pair, 4 pair end (stores issued).  The marks are the start of group 1 and of group 6
