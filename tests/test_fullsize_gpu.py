@@ -65,7 +65,9 @@ def _oracle_apply_crop(g1, g2, ks, b, y0, x0, h, w):
 
 
 def test_c2_fused_apply_timed_instance_vs_oracle_and_generic(c2):
-    """The launch bench.py times: sepconv_gray_mfma<2,4,16,2,true,2> (64-row shape, chosen because B*tiles >= 1024)."""
+    """The launches bench.py times at C2.  Blocked coefficients (bench.py's default, the product's inference path):
+    sepconv_gray_mfma_pair_hp<4,16,2>, the multi-pass row-pair kernel, since the row-pair changes (64-row tiles, B*tiles >= 512).
+    NCHW coefficients (bench.py --nchw): sepconv_gray_mfma<2,4,16,2,true,2> (64-row shape, chosen because B*tiles >= 1024)."""
     from native_instances import instance
     g1, g2, ks = c2
     out = interp_apply_gray(g1, g2, *ks)                     # the single-plane entry point (product inference path)
