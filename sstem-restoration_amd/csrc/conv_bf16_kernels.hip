@@ -27,6 +27,7 @@
 #include <stdlib.h>
 
 #include "conv_kernels.h"
+#include "conv_launch.h"
 
 namespace sstem {
 
@@ -957,17 +958,12 @@ bool conv3x3_bf16_supported(int N, int Cin, int H, int W, int Cout)
     return Cin > 0 && fits && (int64_t)N * ncb * 8 <= 65535;
 }
 
-// K slices for small grids (the rule of conv3x3_ksplit, on 16-channel chunks)
+// K slices for small grids (conv_ksplit, on 16-channel chunks)
 int conv3x3_bf16_ksplit(int N, int Cin, int H, int W, int Cout)
 {
-    static const bool off = [] { const char* e = getenv("SSTEM_CONV_KSPLIT"); return e && atoi(e) == 0; }();
-    if (off) return 1;
     const int CO = conv3x3_bf16_co_block(Cout);
     const int ncb = (Cout + CO - 1) / CO, nchunks = (Cin + BKC - 1) / BKC;
-    const int64_t wgs = (int64_t)((W + BTW - 1) / BTW) * ((H + BTH - 1) / BTH) * N * ncb;
-    int ks = 1;
-    while (wgs * ks < 512 && ks < 8 && nchunks % (ks * 2) == 0 && nchunks / (ks * 2) >= 2) ks *= 2;
-    return ks;
+    return conv_ksplit((int64_t)((W + BTW - 1) / BTW) * ((H + BTH - 1) / BTH) * N * ncb, nchunks, 512, 2);
 }
 
 int64_t conv3x3_bf16_forward_workspace_floats(int N, int Cin, int H, int W, int Cout)
@@ -989,6 +985,7 @@ hipError_t launch_conv3x3_bf16_mfma_io(const void* in, int in_bf16, const float*
                                        int N, int Cin, int H, int W, int Cout, int act, float slope, int w_transposed_flipped,
                                        hipStream_t s, const uint8_t* in_mask, uint8_t* out_mask)
 {
+    // plan: K slices when the workspace has room for them, 16-byte or dword staging, masks
     if (!conv3x3_bf16_supported(N, Cin, H, W, Cout)) return hipErrorInvalidValue;
     const int CO = conv3x3_bf16_co_block(Cout);
     const int ncb = (Cout + CO - 1) / CO, nchunks = (Cin + BKC - 1) / BKC;
@@ -996,55 +993,41 @@ hipError_t launch_conv3x3_bf16_mfma_io(const void* in, int in_bf16, const float*
     __bf16* wp = reinterpret_cast<__bf16*>(workspace);
     const bool prepacked = (w_transposed_flipped & 2) != 0;      // SSTEM_CONV_WEIGHT_PREPACKED, as in launch_conv3x3_mfma
     w_transposed_flipped &= 1;
-    hipError_t e = hipSuccess;
-    if (!prepacked) {
-        hipLaunchKernelGGL(pack_weights_3x3_bf16, dim3(grid_1d_bf(welems, 256)), dim3(256), 0, s, w, wp, Cin, Cout, CO, nchunks,
-                           ncb, w_transposed_flipped);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
     int ksplit = conv3x3_bf16_ksplit(N, Cin, H, W, Cout);
     const int64_t out_elems = (int64_t)N * Cout * H * W;
     if (ksplit > 1 && workspace_floats < welems / 2 + (int64_t)ksplit * out_elems) ksplit = 1;
     if (out_bf16 && ksplit > 1) return hipErrorInvalidValue;
     float* slab = workspace + welems / 2;
     const dim3 grid((W + BTW - 1) / BTW, (H + BTH - 1) / BTH, (unsigned)(N * ncb * ksplit));
-    static const bool novec = [] { const char* e = getenv("SSTEM_BF16_NOVEC"); return e && atoi(e) != 0; }();     // developer knob (A/B runs)
-    const bool vec = (!novec || in_bf16) && W % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
+    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
     if (in_bf16 && !vec) return hipErrorInvalidValue;
     if (!vec && (int64_t)Cin * H * W * 4 >= (int64_t)OOB) return hipErrorInvalidValue;      // dword path: whole image below 2 GiB
-    static const int remap_knob = [] { const char* e = getenv("SSTEM_XCD_REMAP"); return e ? atoi(e) : 1; }();    // developer knob (A/B runs)
-    const int remap = (remap_knob && (int64_t)grid.x * grid.y * grid.z < ((int64_t)1 << 31)) ? 1 : 0;   // 32-bit linear tile ids in the kernel
+    const int remap = (int64_t)grid.x * grid.y * grid.z < ((int64_t)1 << 31) ? 1 : 0;        // 32-bit linear tile ids in the kernel
     const bool masked = in_mask != nullptr || out_mask != nullptr;
     if (masked && !vec) return hipErrorInvalidValue;                       // masks: 16-byte staging
     if (in_mask && in_bf16) return hipErrorInvalidValue;                   // ... and in_mask an fp32 input
     uint8_t* kernel_out_mask = ksplit > 1 ? nullptr : out_mask;             // a launch split over K leaves the mask to its slice-sum launch
-#define SSTEM_BF16_FWD(A, B, V, IB, OB)                                                                                          \
-    hipLaunchKernelGGL((conv3x3_bf16_mfma<A, B, 2, V, IB, OB>), grid, dim3(256), 0, s, in, wp, bias, scale, shift, out, N, Cin, H, W, \
-                       Cout, nchunks, ncb, act, slope, ksplit, slab, remap)
-#define SSTEM_BF16_FWD_M(A, B, IB, OB)                                                                                           \
-    hipLaunchKernelGGL((conv3x3_bf16_mfma<A, B, 2, true, IB, OB, true>), grid, dim3(256), 0, s, in, wp, bias, scale, shift, out, N,  \
-                       Cin, H, W, Cout, nchunks, ncb, act, slope, ksplit, slab, remap, in_mask, kernel_out_mask)
-#define SSTEM_BF16_SHAPE(A, B)                                                                       \
-    do {                                                                                             \
-        if (masked && in_bf16) { if (out_bf16) SSTEM_BF16_FWD_M(A, B, true, true); else SSTEM_BF16_FWD_M(A, B, true, false); } \
-        else if (masked) { if (out_bf16) SSTEM_BF16_FWD_M(A, B, false, true); else SSTEM_BF16_FWD_M(A, B, false, false); } \
-        else                                                                                         \
-        if (!vec) { if (out_bf16) SSTEM_BF16_FWD(A, B, false, false, true); else SSTEM_BF16_FWD(A, B, false, false, false); } \
-        else if (in_bf16 && out_bf16) SSTEM_BF16_FWD(A, B, true, true, true);                        \
-        else if (in_bf16) SSTEM_BF16_FWD(A, B, true, true, false);                                   \
-        else if (out_bf16) SSTEM_BF16_FWD(A, B, true, false, true);                                  \
-        else SSTEM_BF16_FWD(A, B, true, false, false);                                               \
-    } while (0)
-    if (CO == 64) SSTEM_BF16_SHAPE(2, 2); else SSTEM_BF16_SHAPE(1, 4);
-#undef SSTEM_BF16_SHAPE
-#undef SSTEM_BF16_FWD_M
-#undef SSTEM_BF16_FWD
-    e = hipGetLastError();
+    // pack
+    hipError_t e = hipSuccess;
+    if (!prepacked) {
+        e = launch_kernel<pack_weights_3x3_bf16>(dim3(grid_1d_bf(welems, 256)), dim3(256), 0, s, w, wp, Cin, Cout, CO, nchunks, ncb,
+                                                 w_transposed_flipped);
+        if (e != hipSuccess) return e;
+    }
+    // dispatch: channel block x staging x tensor formats x masks; a bf16 input and masks exist with the 16-byte staging only
+    e = with_flags([&](auto co64, auto v, auto inb, auto outb, auto m) -> hipError_t {
+        if constexpr ((inb() || m()) && !v()) {
+            return hipErrorInvalidValue;           // (refused above)
+        } else {
+            return launch_kernel<conv3x3_bf16_mfma<co64() ? 2 : 1, co64() ? 2 : 4, 2, v(), inb(), outb(), m()>>(
+                grid, dim3(256), 0, s, in, wp, bias, scale, shift, out, N, Cin, H, W, Cout, nchunks, ncb, act, slope, ksplit, slab, remap, in_mask,
+                kernel_out_mask);
+        }
+    }, CO == 64, vec, in_bf16 != 0, out_bf16 != 0, masked);
     if (e != hipSuccess || ksplit == 1) return e;
-    hipLaunchKernelGGL(conv3x3_bf16_splitk_epilogue, dim3(grid_1d_bf(out_elems, 256)), dim3(256), 0, s, slab, bias, scale,
-                       shift, static_cast<float*>(out), out_elems, (int64_t)H * W, Cout, ksplit, act, slope, out_mask);
-    return hipGetLastError();
+    // epilogue: the slice sum
+    return launch_kernel<conv3x3_bf16_splitk_epilogue>(dim3(grid_1d_bf(out_elems, 256)), dim3(256), 0, s, slab, bias, scale, shift,
+                                                       static_cast<float*>(out), out_elems, (int64_t)H * W, Cout, ksplit, act, slope, out_mask);
 }
 
 hipError_t launch_conv3x3_bf16_mfma(const float* in, const float* w, const float* bias, const float* scale,
@@ -1066,19 +1049,12 @@ hipError_t launch_conv3x3_bf16_mfma(const float* in, const float* w, const float
 struct WgradBf16Plan { int CinP, CoutP, ksplit, tx, ty; };
 static WgradBf16Plan wgrad_bf16_plan(int N, int Cin, int H, int W, int Cout)
 {
-    static const int target = [] { const char* e = getenv("SSTEM_WGRAD_BF16_TARGET"); return e ? atoi(e) : 256; }();
-    static const int min_tiles = [] { const char* e = getenv("SSTEM_WGRAD_BF16_MIN_TILES"); return e ? atoi(e) : 8; }();
     WgradBf16Plan p;
     p.CinP = (Cin + 63) / 64 * 64;
     p.CoutP = (Cout + 63) / 64 * 64;
     p.tx = (W + BTW - 1) / BTW;
     p.ty = (H + 1) / 2;
-    const int64_t ntiles = (int64_t)N * p.tx * p.ty;
-    const int blocks = (p.CinP / 64) * (p.CoutP / 64);
-    int64_t k = (target + blocks - 1) / blocks;
-    if (k > ntiles / min_tiles) k = ntiles / min_tiles;
-    if (k < 1) k = 1;
-    p.ksplit = (int)k;
+    p.ksplit = wgrad_slabs(256, (p.CinP / 64) * (p.CoutP / 64), (int64_t)N * p.tx * p.ty, 8);
     return p;
 }
 
@@ -1101,27 +1077,20 @@ hipError_t launch_conv3x3_wgrad_bf16_mfma_in(const void* in, int in_bf16, const 
     const WgradBf16Plan p = wgrad_bf16_plan(N, Cin, H, W, Cout);
     float* bias_slab = gb ? workspace + (int64_t)p.ksplit * wgrad_slab_floats(p.CoutP, p.CinP) : nullptr;
     const int blocks = (p.CinP / 64) * (p.CoutP / 64);
-    static const bool novec = [] { const char* e = getenv("SSTEM_BF16_NOVEC"); return e && atoi(e) != 0; }();     // developer knob (A/B runs)
-    static const int runs = [] { const char* e = getenv("SSTEM_WGRAD_RUNS"); return e ? atoi(e) : 2; }();          // developer knob: 0 strided, 1 runs along x, 2 runs down a column strip
-    const bool vec = (!novec || in_bf16) && W % 4 == 0 && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(g)) & 15) == 0;
+    const int runs = 2;                  // a workgroup's pixel tiles: runs down a column strip (0: strided, 1: runs along x)
+    const bool vec = W % 4 == 0 && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(g)) & 15) == 0;
     if (in_bf16 && !vec) return hipErrorInvalidValue;
     if (g_mask && !vec) return hipErrorInvalidValue;
-    if (g_mask && in_bf16)
-        hipLaunchKernelGGL((conv3x3_wgrad_bf16_mfma<true, true, true>), dim3((unsigned)(blocks * p.ksplit)), dim3(512), 0, s, in, g, workspace, N,
-                           Cin, H, W, Cout, p.CinP, p.CoutP, p.ksplit, p.tx, p.ty, bias_slab, runs, g_mask);
-    else if (g_mask)
-        hipLaunchKernelGGL((conv3x3_wgrad_bf16_mfma<true, false, true>), dim3((unsigned)(blocks * p.ksplit)), dim3(512), 0, s, in, g, workspace, N,
-                           Cin, H, W, Cout, p.CinP, p.CoutP, p.ksplit, p.tx, p.ty, bias_slab, runs, g_mask);
-    else if (vec && in_bf16)
-        hipLaunchKernelGGL((conv3x3_wgrad_bf16_mfma<true, true>), dim3((unsigned)(blocks * p.ksplit)), dim3(512), 0, s, in, g, workspace, N, Cin,
-                           H, W, Cout, p.CinP, p.CoutP, p.ksplit, p.tx, p.ty, bias_slab, runs);
-    else if (vec)
-        hipLaunchKernelGGL(conv3x3_wgrad_bf16_mfma<true>, dim3((unsigned)(blocks * p.ksplit)), dim3(512), 0, s, in, g, workspace, N, Cin,
-                           H, W, Cout, p.CinP, p.CoutP, p.ksplit, p.tx, p.ty, bias_slab, runs);
-    else
-        hipLaunchKernelGGL(conv3x3_wgrad_bf16_mfma<false>, dim3((unsigned)(blocks * p.ksplit)), dim3(512), 0, s, in, g, workspace, N, Cin,
-                           H, W, Cout, p.CinP, p.CoutP, p.ksplit, p.tx, p.ty, bias_slab, runs);
-    hipError_t e = hipGetLastError();
+    // dispatch: staging x input format x mask; a bf16 input and the mask exist with the 16-byte staging only
+    hipError_t e = with_flags([&](auto v, auto inb, auto m) -> hipError_t {
+        if constexpr ((inb() || m()) && !v()) {
+            return hipErrorInvalidValue;           // (refused above)
+        } else {
+            return launch_kernel<conv3x3_wgrad_bf16_mfma<v(), inb(), m()>>(dim3((unsigned)(blocks * p.ksplit)), dim3(512), 0, s, in, g, workspace, N,
+                                                                           Cin, H, W, Cout, p.CinP, p.CoutP, p.ksplit, p.tx, p.ty, bias_slab, runs,
+                                                                           g_mask);
+        }
+    }, vec, in_bf16 != 0, g_mask != nullptr);
     if (e != hipSuccess) return e;
     return launch_conv3x3_wgrad_reduce(workspace, gw, Cin, Cout, p.CinP, p.CoutP, p.ksplit, bias_slab, gb, p.ksplit, s, accumulate);
 }

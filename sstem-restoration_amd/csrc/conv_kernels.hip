@@ -26,6 +26,7 @@
 #include <stdlib.h>
 
 #include "conv_kernels.h"
+#include "conv_launch.h"
 
 namespace sstem {
 
@@ -477,50 +478,6 @@ __global__ __launch_bounds__(256) void conv3x3_splitk_epilogue(
         v = apply_act(v, act, slope);
         if (residual) v = (v + residual[i]) * res_scale;
         out[i] = v;
-    }
-}
-
-// The same sum for a convolution that feeds a train-mode BatchNorm: out = sum of slices + bias, and the batch-statistics
-// partials ride along.  Workgroup = one (sample, channel, piece) chunk of up to SPLITK_BN_CHUNK consecutive floats (the chunking of
-// norm_kernels.hip); it writes (count, mean, M2) of its chunk -- mean first, then M2 around it from the values it has just
-// written (its own stores: same thread, same addresses) -- to bn_part[(co * (N * pieces) + n * pieces + piece) * 3 ..].
-constexpr int SPLITK_BN_CHUNK = 16384;
-__global__ __launch_bounds__(256) void conv3x3_splitk_epilogue_bn(
-    const float* __restrict__ slab, const float* __restrict__ bias, float* __restrict__ out, int64_t total, int64_t plane,
-    int Cout, int ksplit, int pieces, float* __restrict__ bn_part)
-{
-    __shared__ float sh[256];
-    const int co = blockIdx.y, n = blockIdx.x / pieces, piece = blockIdx.x % pieces;
-    const int64_t start = (int64_t)piece * SPLITK_BN_CHUNK;
-    const int64_t len = plane - start < SPLITK_BN_CHUNK ? plane - start : SPLITK_BN_CHUNK;
-    const int64_t base = ((int64_t)n * Cout + co) * plane + start;
-    const float bs = bias ? bias[co] : 0.f;
-    auto block_sum = [&](float v) -> float {
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-            __syncthreads();
-        }
-        const float r = sh[0];
-        __syncthreads();
-        return r;
-    };
-    float s1 = 0.f;
-    for (int64_t i = threadIdx.x; i < len; i += 256) {
-        float v = slab[base + i];
-        for (int k = 1; k < ksplit; ++k) v += slab[(int64_t)k * total + base + i];
-        v += bs;
-        out[base + i] = v;
-        s1 += v;
-    }
-    const float mean = block_sum(s1) / (float)len;
-    float s2 = 0.f;
-    for (int64_t i = threadIdx.x; i < len; i += 256) { const float d = out[base + i] - mean; s2 += d * d; }
-    const float m2 = block_sum(s2);
-    if (threadIdx.x == 0) {
-        float* dst = bn_part + ((int64_t)co * gridDim.x + blockIdx.x) * 3;
-        dst[0] = (float)len; dst[1] = mean; dst[2] = m2;
     }
 }
 
@@ -1293,12 +1250,11 @@ static inline int grid_1d(int64_t n, int threads)
     return (int)g;
 }
 
+// output channels per workgroup.  Measured on MI355X: 32-channel blocks (40 KB LDS, 4 workgroups per CU) beat 64 on every layer shape
 int conv3x3_co_block(int Cout)
 {
-    static const int forced = [] { const char* e = getenv("SSTEM_CONV_CO"); return e ? atoi(e) : 0; }();
-    if (forced == 32 || forced == 64) return forced;   // developer knob for A/B runs
     (void)Cout;
-    return 32;   // measured on MI355X: 32-channel blocks (40 KB LDS, 4 workgroups per CU) beat 64 on every layer shape
+    return 32;
 }
 
 int64_t conv3x3_workspace_floats(int Cin, int Cout)
@@ -1308,39 +1264,26 @@ int64_t conv3x3_workspace_floats(int Cin, int Cout)
     return (int64_t)ncb * nchunks * KK * CO;
 }
 
-// K slices for small grids.  A workgroup owns an 8x32-pixel x 32/64-channel tile and walks all of K; when the tile count
-// is below two workgroups per CU (deep layers at small batch: 64 workgroups at N = 2, 512 channels, 16x16 -- measured
-// 4.5x less efficient per sample than the same layer at N = 16) K is cut into 2, 4 or 8 slices.  Pure function of the
-// problem size; slices divide the chunk count evenly and keep at least two chunks each (double-buffered pipeline).
 // Tile geometry of conv3x3_mfma, a pure function of the problem size:
-//   tile width 32, or 16 on maps up to 16 pixels wide (two image rows per MFMA row; SSTEM_CONV_NARROW=0: off);
-//   two MFMA rows per wave (8-row tiles), or one (4-row tiles) when the 8-row tiling gives fewer than 512 workgroups
-//   (SSTEM_CONV_RPW1=0: off);  then K slices: when the tile count is still below two workgroups per CU (deep layers at small batch)
-//   K is cut into 2, 4 or 8 slices of whole input-channel chunks, at least two chunks each (SSTEM_CONV_KSPLIT=0: off).
-int conv3x3_co_block(int Cout);
+//   tile width 32, or 16 on maps up to 16 pixels wide (two image rows per MFMA row);
+//   two MFMA rows per wave (8-row tiles), or one (4-row tiles) when the 8-row tiling gives fewer than 512 workgroups;
+//   then K slices (conv_ksplit): when the tile count is still below two workgroups per CU (deep layers at small batch: 64 workgroups
+//   at N = 2, 512 channels, 16x16 -- measured 4.5x less efficient per sample than the same layer at N = 16).
+constexpr int CONV_WG_TARGET = 512;
 struct ConvGeom { int tw, th, rpw, ksplit, tiles_x, tiles_y; };
 static ConvGeom conv_geom(int N, int Cin, int H, int W, int Cout)
 {
-    static const bool narrow = [] { const char* e = getenv("SSTEM_CONV_NARROW"); return !(e && atoi(e) == 0); }();
-    static const bool rpw1 = [] { const char* e = getenv("SSTEM_CONV_RPW1"); return !(e && atoi(e) == 0); }();
-    static const bool ks_off = [] { const char* e = getenv("SSTEM_CONV_KSPLIT"); return e && atoi(e) == 0; }();
-    static const int wg_target = [] { const char* e = getenv("SSTEM_CONV_WG_TARGET"); return e && atoi(e) > 0 ? atoi(e) : 512; }();   // developer knob
     const int CO = conv3x3_co_block(Cout);
     const int ncb = (Cout + CO - 1) / CO, nchunks = (Cin + KC - 1) / KC;
     ConvGeom g;
-    g.tw = (narrow && W <= 16 && CO == 32) ? 16 : 32;
+    g.tw = W <= 16 ? 16 : 32;
     const int rm = 32 / g.tw;
-    g.rpw = 2;
     g.tiles_x = (W + g.tw - 1) / g.tw;
     auto wgs_for = [&](int rpw) { const int th = 4 * rpw * rm; return (int64_t)g.tiles_x * ((H + th - 1) / th) * N * ncb; };
-    if (rpw1 && CO == 32 && wgs_for(2) < wg_target) g.rpw = 1;
+    g.rpw = wgs_for(2) < CONV_WG_TARGET ? 1 : 2;
     g.th = 4 * g.rpw * rm;
     g.tiles_y = (H + g.th - 1) / g.th;
-    const int64_t wgs = wgs_for(g.rpw);
-    int ks = 1;
-    if (!ks_off)
-        while (wgs * ks < wg_target && ks < 8 && nchunks % (ks * 2) == 0 && nchunks / (ks * 2) >= 2) ks *= 2;
-    g.ksplit = ks;
+    g.ksplit = conv_ksplit(wgs_for(g.rpw), nchunks, CONV_WG_TARGET, 2);
     return g;
 }
 
@@ -1355,15 +1298,11 @@ int64_t conv3x3_forward_workspace_floats(int N, int Cin, int H, int W, int Cout)
 // number of (count, mean, M2) partials per channel a launch with ex.bn_part writes (the caller sizes bn_part = Cout * this * 3)
 int64_t conv3x3_bn_partials(int N, int Cin, int H, int W, int Cout)
 {
-    // A launch split over K leaves the statistics to the BatchNorm's own pass: measured at batch 2 (profiles/r02), the slice-sum
-    // kernel that also produced them (conv3x3_splitk_epilogue_bn, one workgroup per (sample, channel, piece) with two block
-    // reductions) took 25.8 us per layer against 6.3 + 6.2 us for the plain slice sum + the BatchNorm partial pass on these
-    // small tensors.  SSTEM_SPLITK_BN=1 brings it back (A/B runs).
-    static const bool splitk_bn = [] { const char* e = getenv("SSTEM_SPLITK_BN"); return e && atoi(e) != 0; }();
+    // A launch split over K leaves the statistics to the BatchNorm's own pass: measured at batch 2 (profiles/r02), a slice-sum
+    // kernel that also produced them (one workgroup per (sample, channel, piece) with two block reductions) took 25.8 us per layer
+    // against 6.3 + 6.2 us for the plain slice sum + the BatchNorm partial pass on these small tensors.
     const ConvGeom g = conv_geom(N, Cin, H, W, Cout);
-    if (g.ksplit > 1)
-        return splitk_bn ? (int64_t)N * (((int64_t)H * W + SPLITK_BN_CHUNK - 1) / SPLITK_BN_CHUNK) : 0;
-    return (int64_t)N * g.tiles_x * g.tiles_y;
+    return g.ksplit > 1 ? 0 : (int64_t)N * g.tiles_x * g.tiles_y;
 }
 
 hipError_t launch_conv3x3_mfma(const float* in, const float* w, const float* bias, const float* scale,
@@ -1375,71 +1314,39 @@ hipError_t launch_conv3x3_mfma(const float* in, const float* w, const float* bia
     // weights (an earlier call with the same weights, orientation and sizes wrote them): no pack launch
     const bool prepacked = (w_transposed_flipped & 2) != 0;
     w_transposed_flipped &= 1;
+    // plan: geometry; K slices only when the caller's workspace has room for them (sstem_conv3x3_forward_workspace_floats)
     const int CO = conv3x3_co_block(Cout);
     const int ncb = (Cout + CO - 1) / CO, nchunks = (Cin + KC - 1) / KC;
     const int64_t wtotal = (int64_t)ncb * nchunks * KK * CO;
-    hipError_t e = hipSuccess;
-    if (!prepacked) {
-        hipLaunchKernelGGL(pack_weights_3x3, dim3(grid_1d(wtotal, 256)), dim3(256), 0, s, w, workspace, Cin,
-                           Cout, CO, nchunks, ncb, w_transposed_flipped);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    // split K only when the caller's workspace has room for the slices (sstem_conv3x3_forward_workspace_floats)
     const ConvGeom gm = conv_geom(N, Cin, H, W, Cout);
-    int ksplit = gm.ksplit;
     const int64_t out_elems = (int64_t)N * Cout * H * W;
-    if (ksplit > 1 && workspace_floats < wtotal + (int64_t)ksplit * out_elems) {
-        if (ex_in.bn_part) return hipErrorInvalidValue;      // the partial layout follows conv3x3_ksplit: the full workspace is required
-        ksplit = 1;
-    }
-    float* slab = workspace + wtotal;
+    // statistics partials: of the raw conv + bias only, and never of a launch split over K (conv3x3_bn_partials says 0 there)
+    if (ex_in.bn_part && (gm.ksplit > 1 || scale || shift || act != 0 || ex_in.residual)) return hipErrorInvalidValue;
+    const int ksplit = (gm.ksplit > 1 && workspace_floats < wtotal + (int64_t)gm.ksplit * out_elems) ? 1 : gm.ksplit;
     if ((int64_t)N * ncb * ksplit > 65535) return hipErrorInvalidValue;
     const dim3 grid((unsigned)gm.tiles_x, (unsigned)gm.tiles_y, (unsigned)(N * ncb * ksplit));
     const size_t lds_bytes = 2 * (size_t)(IN_TILE + KK * CO) * sizeof(float);      // (the 16-wide tile needs 2592 of the 2720 input floats)
-    static const int remap_knob = [] { const char* e = getenv("SSTEM_XCD_REMAP"); return e ? atoi(e) : 1; }();     // developer knob (A/B runs)
-    const int remap = (remap_knob && (int64_t)grid.x * grid.y * grid.z < ((int64_t)1 << 31)) ? 1 : 0;   // 32-bit linear tile ids in the kernel
+    const int remap = (int64_t)grid.x * grid.y * grid.z < ((int64_t)1 << 31) ? 1 : 0;   // 32-bit linear tile ids in the kernel
+    float* slab = workspace + wtotal;
     ConvExtra ex = ex_in;
     ex.bn_tiles = (int)(N * grid.x * grid.y);
-    if (ex.bn_part && (scale || shift || act != 0 || ex.residual)) return hipErrorInvalidValue;   // statistics of the raw conv + bias only
-    if (CO == 64) {
-        auto k = conv3x3_mfma<2>;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    // pack
+    hipError_t e = hipSuccess;
+    if (!prepacked) {
+        e = launch_kernel<pack_weights_3x3>(dim3(grid_1d(wtotal, 256)), dim3(256), 0, s, w, workspace, Cin, Cout, CO, nchunks, ncb,
+                                            w_transposed_flipped);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, grid, dim3(256), lds_bytes, s, in, workspace, bias, scale, shift, out, N, Cin, H, W,
-                           Cout, nchunks, ncb, act, slope, ksplit, slab, remap, ex);
-    } else if (gm.tw == 16 || gm.rpw == 1) {
-#define SSTEM_CONV_VARIANT(WT_, RPW_)                                                                                               \
-    {                                                                                                                               \
-        auto k = conv3x3_mfma<1, WT_, RPW_>;                                                                                        \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);     \
-        if (e != hipSuccess) return e;                                                                                              \
-        hipLaunchKernelGGL(k, grid, dim3(256), lds_bytes, s, in, workspace, bias, scale, shift, out, N, Cin, H, W, Cout, nchunks,   \
-                           ncb, act, slope, ksplit, slab, remap, ex);                                                               \
     }
-        if (gm.tw == 16 && gm.rpw == 1) SSTEM_CONV_VARIANT(16, 1)
-        else if (gm.tw == 16) SSTEM_CONV_VARIANT(16, 2)
-        else SSTEM_CONV_VARIANT(32, 1)
-#undef SSTEM_CONV_VARIANT
-    } else {
-        auto k = conv3x3_mfma<1>;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, grid, dim3(256), lds_bytes, s, in, workspace, bias, scale, shift, out, N, Cin, H, W,
-                           Cout, nchunks, ncb, act, slope, ksplit, slab, remap, ex);
-    }
-    e = hipGetLastError();
+    // dispatch: tile width x MFMA rows per wave
+    e = with_flags([&](auto narrow, auto one_row) {
+        return launch_kernel<conv3x3_mfma<1, narrow() ? 16 : 32, one_row() ? 1 : 2>>(grid, dim3(256), lds_bytes, s, in, workspace, bias, scale,
+                                                                                   shift, out, N, Cin, H, W, Cout, nchunks, ncb, act,
+                                                                                   slope, ksplit, slab, remap, ex);
+    }, gm.tw == 16, gm.rpw == 1);
     if (e != hipSuccess || ksplit == 1) return e;
-    if (ex.bn_part) {
-        const int pieces = (int)(((int64_t)H * W + SPLITK_BN_CHUNK - 1) / SPLITK_BN_CHUNK);
-        if (Cout > 65535) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(conv3x3_splitk_epilogue_bn, dim3((unsigned)(N * pieces), (unsigned)Cout), dim3(256), 0, s, slab, bias, out,
-                           out_elems, (int64_t)H * W, Cout, ksplit, pieces, ex.bn_part);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(conv3x3_splitk_epilogue, dim3(grid_1d(out_elems, 256)), dim3(256), 0, s, slab, bias, scale, shift,
-                       out, out_elems, (int64_t)H * W, Cout, ksplit, act, slope, ex.residual, ex.res_scale);
-    return hipGetLastError();
+    // epilogue: the slice sum
+    return launch_kernel<conv3x3_splitk_epilogue>(dim3(grid_1d(out_elems, 256)), dim3(256), 0, s, slab, bias, scale, shift, out, out_elems,
+                                                  (int64_t)H * W, Cout, ksplit, act, slope, ex.residual, ex.res_scale);
 }
 
 hipError_t launch_pack_weights_3x3_both(const float* w, float* wp_f, float* wp_t, int Cin, int Cout, hipStream_t s)
@@ -1881,93 +1788,44 @@ static WgradPlan wgrad_plan(int N, int Cin, int H, int W, int Cout)
 {
     // Candidates: the first-generation 4-wave 2x2 kernel (2-row tiles, two workgroups per CU) and the 8-wave kernels with K split
     // over the waves -- (2,2,2,2) / (2,2,2,1): 64 x 64 blocks on 4- / 2-row tiles; (1,2,4,1) / (2,1,4,1): 32 x 64 / 64 x 32 blocks;
-    // (1,1,8,1): 32 x 32 blocks, eight waves per slab.  For each, and for each number of slabs, a small cost model:
-    //   matrix time    = rounds x tiles per workgroup x (tile pixels x block co x block ci x 18 flop) / (70 % of a CU's fp32 MFMA rate)
-    //   fixed cost     = 12 us per round of workgroups (first-tile latency, in-workgroup reduction, slab store)
-    //   slab traffic   = slabs x 9 x CoutP x CinP x 4 B written and read back by the reduce launch, at 2.5 TB/s, + 4 us
-    //   operand reads  = every co block re-reads the input tiles (with their halo rows), every ci block the gradient tiles, at 3 TB/s
-    // and the cheapest wins.  What the model encodes is what the traces showed (profiles/r02): the deep layers of a 2-sample step
-    // ran on 64 workgroups with 2 tiles each (52 us for 1.2 GFLOP), the thin layers paid 68-134 us of reduce for 256 slabs, and a
-    // channel count <= 32 wasted whole quadrants.  Pure function of the problem size: the workspace query sees the same plan.
-    // SSTEM_WGRAD_V2=0: the first-generation kernels only (A/B runs).
-    static const int v2_knob = [] { const char* e = getenv("SSTEM_WGRAD_V2"); return e ? atoi(e) : 1; }();
-    static const int small = [] { const char* e = getenv("SSTEM_WGRAD_SMALL"); return e ? atoi(e) : -1; }();
-    static const int target_knob = [] { const char* e = getenv("SSTEM_WGRAD_TARGET"); return e && atoi(e) > 0 ? atoi(e) : 512; }();   // developer knob; measured on the
-    // fusion step (profiles/r02): 1024 -> 512 halves the slab traffic of the reduce launch, batch 16 step 24.17 -> 23.68 ms, batch 2 unchanged
-    static const int min_tiles = [] { const char* e = getenv("SSTEM_WGRAD_MIN_TILES"); return e && atoi(e) > 0 ? atoi(e) : 4; }();   // developer knob
+    // (1,1,8,1): 32 x 32 blocks, eight waves per slab.  Pure function of the problem size: the workspace query sees the same plan.
     WgradPlan p;
-    p.wt = 32;
-    p.tx = (W + TW - 1) / TW;
-    const int64_t tiles_2x32 = (int64_t)N * p.tx * ((H + WT_R - 1) / WT_R);
+    // one candidate: block and tile shape, padded channel counts, slabs (wgrad_slabs); returns the workgroups it gives
+    auto set = [&](int wco, int wci, int wk, int rpw, int wt, int wg_target, int min_tiles_per_wg, int slabs) {
+        const int bco = 32 * wco, bci = 32 * wci, tr = wk * rpw * (32 / wt);
+        p.wco = wco; p.wci = wci; p.wk = wk; p.rpw = rpw; p.v2 = wk > 1; p.wt = wt;
+        p.tx = (W + wt - 1) / wt;
+        p.CinP = (Cin + bci - 1) / bci * bci; p.CoutP = (Cout + bco - 1) / bco * bco;
+        p.ty = (H + tr - 1) / tr;
+        p.bparts = p.v2 ? 512 / bco : 256 / bco;
+        const int64_t ntiles = (int64_t)N * p.tx * p.ty;
+        const int64_t blocks = (int64_t)(p.CinP / bci) * (p.CoutP / bco);
+        p.ksplit = slabs ? (int)(slabs < ntiles ? slabs : ntiles) : wgrad_slabs(wg_target, blocks, ntiles, min_tiles_per_wg);
+        return blocks * p.ksplit;
+    };
     if (const char* f = getenv("SSTEM_WGRAD_FORCE")) {       // developer knob (tools/sweep_wgrad.py): "wco,wci,wk,rpw,slabs", read at every call
         int a, b, c, d, k;
         if (sscanf(f, "%d,%d,%d,%d,%d", &a, &b, &c, &d, &k) == 5 && (a == 1 || a == 2) && (b == 1 || b == 2) && k >= 1 &&
             ((c == 1 && d == 2 && a == 2 && b == 2) || (a * b * c == 8 && (d == 1 || (d == 2 && a == 2 && b == 2 && c == 2))))) {
-            p.wco = a; p.wci = b; p.wk = c; p.rpw = d; p.v2 = c > 1;
-            const int bco = 32 * a, bci = 32 * b, tr = c * d;
-            p.CinP = (Cin + bci - 1) / bci * bci; p.CoutP = (Cout + bco - 1) / bco * bco;
-            p.ty = (H + tr - 1) / tr;
-            const int64_t ntiles = (int64_t)N * p.tx * p.ty;
-            p.ksplit = (int)(k < ntiles ? k : ntiles);
-            p.bparts = p.v2 ? 512 / bco : 256 / bco;
+            set(a, b, c, d, 32, 0, 0, k);
             return p;
         }
     }
-    if (v2_knob) {
-        // Rules read off a sweep of every configuration x slab count on the layers of the SFF fusion step at 2 and 16 samples
-        // (tools/sweep_wgrad.py, profiles/r02/e_wgrad_sweep.txt; a first version chose by a cost model and was 10-30 % off the
-        // best measured point on most layers):
-        //   a side of <= 32 channels      -> the 8-wave kernel without padded quadrants, one slab per workgroup, ~256 workgroups
-        //   both sides >= 64 channels     -> the first-generation 2x2 kernel, ~512 workgroups (ties with (2,1,4,1) everywhere measured)
-        //   ... unless its 2-row tiles are too few to give 256 workgroups (32x32 maps at small batch): 32x32 blocks, 8 waves per slab
-        //   maps up to 16 pixels wide -> the 8-wave kernels with two image rows per MFMA row (SSTEM_CONV_NARROW=0: off)
-        static const bool narrow_knob = [] { const char* e = getenv("SSTEM_CONV_NARROW"); return !(e && atoi(e) == 0); }();
-        const bool narrow = narrow_knob && W <= 16;
-        auto set = [&](int wco, int wci, int wk, int rpw, bool v2, int wg_target, int min_tiles_per_wg) {
-            const int wt = (v2 && narrow) ? 16 : 32;
-            const int bco = 32 * wco, bci = 32 * wci, tr = wk * rpw * (32 / wt);
-            p.wco = wco; p.wci = wci; p.wk = wk; p.rpw = rpw; p.v2 = v2; p.wt = wt;
-            p.tx = (W + wt - 1) / wt;
-            p.CinP = (Cin + bci - 1) / bci * bci; p.CoutP = (Cout + bco - 1) / bco * bco;
-            p.ty = (H + tr - 1) / tr;
-            p.bparts = v2 ? 512 / bco : 256 / bco;
-            const int64_t ntiles = (int64_t)N * p.tx * p.ty;
-            const int64_t blocks = (int64_t)(p.CinP / bci) * (p.CoutP / bco);
-            int64_t k = (wg_target + blocks - 1) / blocks;
-            if (k > ntiles / min_tiles_per_wg) k = ntiles / min_tiles_per_wg;
-            if (k < 1) k = 1;
-            p.ksplit = (int)k;
-            return blocks * k;
-        };
-        if (Cout <= 32 && Cin <= 32) { set(1, 1, 8, 1, true, 256, 2); return p; }
-        if (Cout <= 32) { set(1, 2, 4, 1, true, 256, 2); return p; }
-        if (Cin <= 32) { set(2, 1, 4, 1, true, 256, 1); return p; }
-        if (narrow) { set(2, 2, 2, 2, true, 256, 1); return p; }
-        if (set(2, 2, 1, 2, false, 512, 2) >= 256) return p;
-        set(1, 1, 8, 1, true, 256, 1);
-        return p;
-    }
-    p.v2 = false; p.wk = 1; p.rpw = WT_R;
-    // first generation.  Workgroup shape measured on MI355X after the staging rewrite (tools/bench_wgrad.py, one box, two
-    // repetitions): the one-wave 32x32 workgroup wins when BOTH channel counts are <= 32 and there are many pixel tiles, loses
-    // when only one side is small and at small batch.  SSTEM_WGRAD_SMALL=0 / 1 forces never / whenever a side is <= 32 (A/B runs).
-    const bool both_small = Cout <= 32 && Cin <= 32 && tiles_2x32 >= 4096;
-    p.wco = (small == 1 ? Cout <= 32 : (small == -1 && both_small)) ? 1 : 2;
-    p.wci = (small == 1 ? Cin <= 32 : (small == -1 && both_small)) ? 1 : 2;
-    const int bco = 32 * p.wco, bci = 32 * p.wci;
-    p.CinP = (Cin + bci - 1) / bci * bci;
-    p.CoutP = (Cout + bco - 1) / bco * bco;
-    p.ty = (H + WT_R - 1) / WT_R;
-    p.bparts = (64 * p.wco * p.wci) / bco;
-    const int64_t ntiles = (int64_t)N * p.tx * p.ty;
-    const int blocks = (p.CinP / bci) * (p.CoutP / bco);
-    // enough workgroups to fill the chip twice (smaller workgroups -> more of them), but keep at least
-    // 4 pixel tiles per workgroup so the partial-slab traffic stays below the useful work
-    const int target = target_knob * 4 / (p.wco * p.wci);
-    int64_t k = (target + blocks - 1) / blocks;
-    if (k > ntiles / min_tiles) k = ntiles / min_tiles;
-    if (k < 1) k = 1;
-    p.ksplit = (int)k;
+    // Rules read off a sweep of every configuration x slab count on the layers of the SFF fusion step at 2 and 16 samples
+    // (tools/sweep_wgrad.py, profiles/r02/e_wgrad_sweep.txt; a first version chose by a cost model and was 10-30 % off the
+    // best measured point on most layers):
+    //   a side of <= 32 channels      -> the 8-wave kernel without padded quadrants, one slab per workgroup, ~256 workgroups
+    //   both sides >= 64 channels     -> the first-generation 2x2 kernel, ~512 workgroups (ties with (2,1,4,1) everywhere measured)
+    //   ... unless its 2-row tiles are too few to give 256 workgroups (32x32 maps at small batch): 32x32 blocks, 8 waves per slab
+    //   maps up to 16 pixels wide -> the 8-wave kernels with two image rows per MFMA row
+    const bool narrow = W <= 16;
+    const int wt = narrow ? 16 : 32;
+    if (Cout <= 32 && Cin <= 32) { set(1, 1, 8, 1, wt, 256, 2, 0); return p; }
+    if (Cout <= 32) { set(1, 2, 4, 1, wt, 256, 2, 0); return p; }
+    if (Cin <= 32) { set(2, 1, 4, 1, wt, 256, 1, 0); return p; }
+    if (narrow) { set(2, 2, 2, 2, wt, 256, 1, 0); return p; }
+    if (set(2, 2, 1, 2, 32, 512, 2, 0) >= 256) return p;
+    set(1, 1, 8, 1, wt, 256, 1, 0);
     return p;
 }
 
@@ -1978,7 +1836,8 @@ int64_t conv3x3_wgrad_workspace_floats(int N, int Cin, int H, int W, int Cout)
     return (int64_t)p.ksplit * wgrad_slab_floats(p.CoutP, p.CinP) + (int64_t)p.ksplit * 16 * p.CoutP;
 }
 
-template <int WCO, int WCI, int WK, int RPW, int WT = 32>
+// one 8-wave instance: its LDS is the larger of the staging images and the in-workgroup reduction
+template <int WCO, int WCI, int WK, int RPW, int WT>
 static hipError_t launch_wgrad_v2(const float* in, const float* g, float* workspace, int N, int Cin, int H, int W, int Cout,
                                   const WgradPlan& p, float* bias_slab, hipStream_t s)
 {
@@ -1987,50 +1846,39 @@ static hipError_t launch_wgrad_v2(const float* in, const float* g, float* worksp
     constexpr int red = NW * 1024;
     constexpr size_t lds_bytes = (size_t)(stage > red ? stage : red) * sizeof(float);
     static_assert(lds_bytes <= 160 * 1024, "LDS");
-    auto k = conv3x3_wgrad_mfma_v2<WCO, WCI, WK, RPW, WT>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
     const int blocks = (p.CinP / (32 * WCI)) * (p.CoutP / (32 * WCO));
-    hipLaunchKernelGGL(k, dim3((unsigned)(blocks * p.ksplit)), dim3(64 * NW), lds_bytes, s, in, g, workspace, N, Cin, H, W, Cout,
-                       p.CinP, p.CoutP, p.ksplit, p.tx, p.ty, bias_slab);
-    return hipGetLastError();
+    return launch_kernel<conv3x3_wgrad_mfma_v2<WCO, WCI, WK, RPW, WT>>(dim3((unsigned)(blocks * p.ksplit)), dim3(64 * NW), lds_bytes, s, in, g,
+                                                                         workspace, N, Cin, H, W, Cout, p.CinP, p.CoutP, p.ksplit, p.tx, p.ty,
+                                                                         bias_slab);
+}
+
+// the plan's block shape names the 8-wave instance; every shape exists on 32- and on 16-wide tiles
+template <int WT>
+static hipError_t launch_wgrad_v2_shape(const float* in, const float* g, float* workspace, int N, int Cin, int H, int W, int Cout,
+                                        const WgradPlan& p, float* bias_slab, hipStream_t s)
+{
+    if (p.wco == 1 && p.wci == 1) return launch_wgrad_v2<1, 1, 8, 1, WT>(in, g, workspace, N, Cin, H, W, Cout, p, bias_slab, s);
+    if (p.wco == 1) return launch_wgrad_v2<1, 2, 4, 1, WT>(in, g, workspace, N, Cin, H, W, Cout, p, bias_slab, s);
+    if (p.wci == 1) return launch_wgrad_v2<2, 1, 4, 1, WT>(in, g, workspace, N, Cin, H, W, Cout, p, bias_slab, s);
+    if (p.rpw == 2) return launch_wgrad_v2<2, 2, 2, 2, WT>(in, g, workspace, N, Cin, H, W, Cout, p, bias_slab, s);
+    return launch_wgrad_v2<2, 2, 2, 1, WT>(in, g, workspace, N, Cin, H, W, Cout, p, bias_slab, s);
 }
 
 hipError_t launch_conv3x3_wgrad_mfma(const float* in, const float* g, float* gw, float* gb, float* workspace, int N, int Cin,
                                      int H, int W, int Cout, hipStream_t s, int accumulate)
 {
     const WgradPlan p = wgrad_plan(N, Cin, H, W, Cout);
-    static const bool plan_debug = [] { const char* e = getenv("SSTEM_WGRAD_PLAN_DEBUG"); return e && atoi(e) != 0; }();   // developer knob
-    if (plan_debug)
-        fprintf(stderr, "wgrad plan N=%d %d->%d %dx%d: %s (%d,%d,%d,%d) blocks %d x slabs %d\n", N, Cin, Cout, H, W, p.v2 ? "v2" : "v1", p.wco, p.wci,
-                p.wk, p.rpw, (p.CinP / (32 * p.wci)) * (p.CoutP / (32 * p.wco)), p.ksplit);
     float* bias_slab = gb ? workspace + (int64_t)p.ksplit * wgrad_slab_floats(p.CoutP, p.CinP) : nullptr;
     const int bias_rows = p.ksplit * p.bparts;
     hipError_t e;
-    if (p.v2 && p.wt == 16) {
-        if (p.wco == 1 && p.wci == 1) e = launch_wgrad_v2<1, 1, 8, 1, 16>(in, g, workspace, N, Cin, H, W, Cout, p, bias_slab, s);
-        else if (p.wco == 1) e = launch_wgrad_v2<1, 2, 4, 1, 16>(in, g, workspace, N, Cin, H, W, Cout, p, bias_slab, s);
-        else if (p.wci == 1) e = launch_wgrad_v2<2, 1, 4, 1, 16>(in, g, workspace, N, Cin, H, W, Cout, p, bias_slab, s);
-        else if (p.rpw == 2) e = launch_wgrad_v2<2, 2, 2, 2, 16>(in, g, workspace, N, Cin, H, W, Cout, p, bias_slab, s);
-        else e = launch_wgrad_v2<2, 2, 2, 1, 16>(in, g, workspace, N, Cin, H, W, Cout, p, bias_slab, s);
-    } else if (p.v2) {
-        if (p.wco == 1 && p.wci == 1) e = launch_wgrad_v2<1, 1, 8, 1>(in, g, workspace, N, Cin, H, W, Cout, p, bias_slab, s);
-        else if (p.wco == 1) e = launch_wgrad_v2<1, 2, 4, 1>(in, g, workspace, N, Cin, H, W, Cout, p, bias_slab, s);
-        else if (p.wci == 1) e = launch_wgrad_v2<2, 1, 4, 1>(in, g, workspace, N, Cin, H, W, Cout, p, bias_slab, s);
-        else if (p.rpw == 2) e = launch_wgrad_v2<2, 2, 2, 2>(in, g, workspace, N, Cin, H, W, Cout, p, bias_slab, s);
-        else e = launch_wgrad_v2<2, 2, 2, 1>(in, g, workspace, N, Cin, H, W, Cout, p, bias_slab, s);
+    if (!p.v2) {          // the first-generation kernel: 64 x 64 blocks only
+        const int blocks = (p.CinP / 64) * (p.CoutP / 64);
+        e = launch_kernel<conv3x3_wgrad_mfma<2, 2>>(dim3((unsigned)(blocks * p.ksplit)), dim3(256), 0, s, in, g, workspace, N, Cin, H, W, Cout,
+                                                    p.CinP, p.CoutP, p.ksplit, p.tx, p.ty, bias_slab);
+    } else if (p.wt == 16) {
+        e = launch_wgrad_v2_shape<16>(in, g, workspace, N, Cin, H, W, Cout, p, bias_slab, s);
     } else {
-        const int blocks = (p.CinP / (32 * p.wci)) * (p.CoutP / (32 * p.wco));
-        const dim3 grid((unsigned)(blocks * p.ksplit));
-#define SSTEM_WGRAD(A, B)                                                                                  \
-    hipLaunchKernelGGL((conv3x3_wgrad_mfma<A, B>), grid, dim3(64 * A * B), 0, s, in, g, workspace, N, Cin, H, W, \
-                       Cout, p.CinP, p.CoutP, p.ksplit, p.tx, p.ty, bias_slab)
-        if (p.wco == 2 && p.wci == 2) SSTEM_WGRAD(2, 2);
-        else if (p.wco == 2) SSTEM_WGRAD(2, 1);
-        else if (p.wci == 2) SSTEM_WGRAD(1, 2);
-        else SSTEM_WGRAD(1, 1);
-#undef SSTEM_WGRAD
-        e = hipGetLastError();
+        e = launch_wgrad_v2_shape<32>(in, g, workspace, N, Cin, H, W, Cout, p, bias_slab, s);
     }
     if (e != hipSuccess) return e;
     return launch_conv3x3_wgrad_reduce(workspace, gw, Cin, Cout, p.CinP, p.CoutP, p.ksplit, bias_slab, gb, bias_rows, s, accumulate);

@@ -120,19 +120,5 @@ __device__ __forceinline__ void amax_word_update(float* __restrict__ word, float
     }
 }
 
-// per kernel instance (`done` belongs to the call site) and device, once: the kernels' dynamic LDS is above the 64 KB default
-inline hipError_t wgrad_split_lds(const void* kernel, int bytes, bool (&done)[64])
-{
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64 || !done[dev]) {
-        e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) done[dev] = true;
-    }
-    return hipSuccess;
-}
-
 }  // namespace
 }  // namespace sstem

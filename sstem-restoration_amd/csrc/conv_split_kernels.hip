@@ -28,6 +28,7 @@
 
 #include "conv_kernels.h"
 #include "conv_split_common.h"
+#include "conv_launch.h"
 
 // developer ablation builds of conv3x3_split_mfma (wrong results; tools/build_ablate_split.sh): 1 no per-item LDS reads of the B operand,
 // 2 no staging commit (split + LDS stores), 4 no staging loads, 8 no A-fragment loads after the first, 64 no epilogue stores (whole tiles);
@@ -1084,32 +1085,20 @@ inline int64_t packed_split_elems(int Cin, int Cout, int P)
 }
 
 // Output channels per workgroup and K slices: a pure function of the problem size (launcher and workspace query).  64 channels per
-// workgroup (two waves share every input fragment) unless that leaves the grid below SSTEM_SPLIT_CO32_BELOW workgroups: then 32
-// (twice the workgroups, every wave its own channel block; default 0 = never: on the 2-sample layers of the fusion step it measured
-// 3-8 % slower than the 64-channel blocks, gpurun_out r5i); K slices of whole 16-channel chunks while the grid is below 512.
+// workgroup (two waves share every input fragment; 32 per workgroup for more workgroups on small grids measured 3-8 % slower on the
+// 2-sample layers of the fusion step), 32 when the layer has no more; K slices of whole 16-channel chunks, at least two each, while
+// the grid is below 512 workgroups (sweep: profiles/r05/n_*).
 struct SplitGeom { int CO, ncb, ksplit; };
-inline bool split_wt16(int W)
-{
-    static const bool off = [] { const char* e = getenv("SSTEM_SPLIT_WT16"); return e && atoi(e) == 0; }();      // developer knob (A/B runs)
-    return !off && W <= 16 && W % 4 == 0;
-}
+inline bool split_wt16(int W) { return W <= 16 && W % 4 == 0; }      // 16 x 16 tiles on maps up to 16 pixels wide
 inline SplitGeom split_geom(int N, int Cin, int H, int W, int Cout)
 {
-    static const int co32_below = [] { const char* e = getenv("SSTEM_SPLIT_CO32_BELOW"); return e ? atoi(e) : 0; }();
-    static const int min_cpk = [] { const char* e = getenv("SSTEM_SPLIT_MIN_CPK"); return e ? atoi(e) : 2; }();
-    static const bool ks_off = [] { const char* e = getenv("SSTEM_CONV_KSPLIT"); return e && atoi(e) == 0; }();
-    static const int ks_below = [] { const char* e = getenv("SSTEM_SPLIT_KSPLIT_BELOW"); return e ? atoi(e) : 512; }();      // (sweep: profiles/r05/n_*)
-    const bool w16 = split_wt16(W);                               // 16 x 16 tiles on maps up to 16 pixels wide
+    const bool w16 = split_wt16(W);
     const int tw = w16 ? 16 : STW, th = w16 ? 16 : STH;
     const int64_t tiles = (int64_t)((W + tw - 1) / tw) * ((H + th - 1) / th) * N;
-    const int nchunks = (Cin + SKC - 1) / SKC;
     SplitGeom g;
-    g.CO = (Cout <= 32 || tiles * ((Cout + 63) / 64) < co32_below) ? 32 : 64;
+    g.CO = Cout <= 32 ? 32 : 64;
     g.ncb = (Cout + g.CO - 1) / g.CO;
-    int ks = 1;
-    if (!ks_off)
-        while (tiles * g.ncb * ks < ks_below && ks < 8 && nchunks % (ks * 2) == 0 && nchunks / (ks * 2) >= min_cpk) ks *= 2;
-    g.ksplit = ks;
+    g.ksplit = conv_ksplit(tiles * g.ncb, (Cin + SKC - 1) / SKC, 512, 2);
     return g;
 }
 
@@ -1126,6 +1115,11 @@ bool conv3x3_split_f16_supported(int N, int Cin, int H, int W, int Cout)
 
 // fp16 pieces: a 16-byte header in front of the packed image + the 1024-slot amax word of the weights behind it
 constexpr int F16_HDR_ELEMS = 8, F16_TAIL_FLOATS = AMAX_SLOTS;
+// bf16 elements at the head of a launch's workspace (the K slices follow)
+static inline int64_t split_workspace_elems(int Cin, int Cout, int pieces, bool f16)
+{
+    return packed_split_elems(Cin, Cout, pieces) + (f16 ? F16_HDR_ELEMS + 2 * F16_TAIL_FLOATS : 0);
+}
 int64_t conv3x3_split_packed_floats(int Cin, int Cout, int pieces, int f16)
 {
     return packed_split_elems(Cin, Cout, pieces) / 2 + (f16 ? F16_HDR_ELEMS / 2 + F16_TAIL_FLOATS : 0);
@@ -1220,23 +1214,90 @@ hipError_t launch_pack_weights_3x3_split_f16_group(const int64_t* table, int n_e
     return hipGetLastError();
 }
 
+// What one call of launch_conv3x3_split_mfma does: a pure function of the sizes, the piece format, the ConvExtra flags, the alignment
+// of the input, the room in the workspace and the values of the three walk variables.
+struct SplitPlan {
+    bool ok;                         // false: the launcher refuses the call (hipErrorInvalidValue)
+    int CO, ncb, ksplit;             // output channels per workgroup, channel blocks, K slices
+    bool vec, w16, tail, masked;     // 16-byte staging, 16 x 16 tiles, tap-row last chunk (split_tail_chunk), an input or output mask
+    int walk;                        // tiles a workgroup of the tile-walking instance walks down the image (0: a per-tile instance)
+    bool ct;                         // the sub-pixel form of a ConvTranspose2d(k3, s2, p1, op1): see the kernel
+    int ctwalk;                      // ... and the tiles its workgroups walk (0: its per-tile instance)
+    dim3 grid;                       // one workgroup per tile, channel block and K slice (a walking launch divides y by its walk)
+};
+static SplitPlan split_forward_plan(int N, int Cin, int H, int W, int Cout, int pieces, const ConvExtra& ex, bool has_out, bool in_aligned16,
+                                    int64_t workspace_floats, int walk_knob, int64_t walk_min_wgs, int ctwalk_knob)
+{
+    SplitPlan p = {};
+    const bool f16 = ex.f16 != 0;
+    if (pieces != 2 && pieces != 3) return p;
+    if (!conv3x3_split_supported(N, Cin, H, W, Cout) || ex.bn_part) return p;
+    if (f16 && !conv3x3_split_f16_supported(N, Cin, H, W, Cout)) return p;
+    if (f16 && (pieces != 2 || !ex.in_amax)) return p;
+    if (f16 && (ex.in_mask || ex.out_mask) && (ex.out_blocked || ex.pool_out || ex.out_img_stride)) return p;   // masks: plain NCHW stores
+    if ((ex.out_blocked == 1 && ex.residual) || (ex.out_blocked && ex.out_mask)) return p;
+    const SplitGeom geo = split_geom(N, Cin, H, W, Cout);
+    p.CO = geo.CO; p.ncb = geo.ncb;
+    p.ct = ex.out_blocked == 2;
+    if (p.ct && (!f16 || Cout % 128 != 0 || Cin % SKC != 0 || W % 4 != 0)) return p;
+    // a pooled copy: whole tiles only (H % 8 == 0, W % 32 == 0), the fp16 id, plain NCHW store without residual, never split over K
+    if (ex.pool_out && (!f16 || ex.out_blocked || ex.residual || H % 8 != 0 || W % 32 != 0 || ex.pool_kind < 1 || ex.pool_kind > 2 ||
+                        (int64_t)Cout * H * W * 4 >= ((int64_t)1 << 32)))      // (whole tiles of one image below 4 GiB: the buffer-resource store path)
+        return p;
+    if (!has_out && !ex.pool_out) return p;                  // no full-resolution output: only next to a pooled copy
+    // K slices: a blocked / shuffled / strided / pooled store is the launch's own, and the slices need room in the workspace
+    p.ksplit = (ex.out_blocked || ex.out_img_stride || ex.pool_out) ? 1 : geo.ksplit;
+    if (p.ksplit > 1 && workspace_floats < split_workspace_elems(Cin, Cout, pieces, f16) / 2 + (int64_t)p.ksplit * N * Cout * H * W) p.ksplit = 1;
+    // 16-byte staging; fp16 pieces: eight channel planes stay below 2^31 bytes (the staging loads' buffer resource, lanes outside at 2^31)
+    p.vec = W % 4 == 0 && in_aligned16 && (!f16 || (int64_t)H * W * 32 < ((int64_t)1 << 31));
+    p.w16 = p.vec && split_wt16(W);
+    const int tw = p.w16 ? 16 : STW, th = p.w16 ? 16 : STH;
+    p.grid = dim3((W + tw - 1) / tw, (H + th - 1) / th, (unsigned)(N * p.ncb * p.ksplit));
+    if (!p.vec && (int64_t)Cin * H * W * 4 >= (int64_t)S_OOB) return p;
+    p.masked = ex.in_mask != nullptr || ex.out_mask != nullptr;
+    p.tail = split_tail_chunk(Cin, pieces, f16);             // the packing's own rule
+    // which launches walk: fp16 pieces, 16-byte staging, 32-wide tiles, no tap-row chunk, no K slices, and enough workgroups left to
+    // fill the chip several times over (walk_knob: 0 = never, n = tiles per workgroup; walk_min_wgs: the smallest grid a walking launch
+    // may be left with).  The 64-channel-block instance does not walk: its second staging set spills -- 256 VGPRs + 59 -- and it is
+    // power-bound: measured 3 % slower.
+    auto walked = [&](int walk, int64_t min_wgs) {
+        while (walk > 1 && (int64_t)p.grid.x * ((p.grid.y + walk - 1) / walk) * p.grid.z < min_wgs) walk >>= 1;
+        return walk < 2 ? 0 : walk;
+    };
+    if (f16 && p.vec && !p.w16 && !p.tail && p.ksplit == 1 && walk_knob > 0 && p.CO == 32 && !p.masked) p.walk = walked(walk_knob, walk_min_wgs);
+    if (p.ct) {
+        if (!p.vec || p.w16 || p.tail || p.CO != 64) return p;
+        p.ctwalk = walked(ctwalk_knob, 2048);
+        p.ok = true;
+        return p;
+    }
+#if SSTEM_SPLIT_DEV      // developer builds (minutes of compile time less): only the 16-byte-staging fp16 instances of 32-wide tiles
+    if (!f16 || p.w16 || !p.vec) return p;
+#endif
+    if (f16 && p.masked && !p.vec) return p;     // masked fp16 instances (recorded launches) exist for the 16-byte staging; the dword path keeps bf16 pieces
+    p.ok = true;
+    return p;
+}
+
 hipError_t launch_conv3x3_split_mfma(const float* in, const float* w, const float* bias, const float* scale, const float* shift,
                                      float* out, float* workspace, int64_t workspace_floats, int N, int Cin, int H, int W, int Cout,
                                      int act, float slope, int w_transposed_flipped, int pieces, hipStream_t s, const ConvExtra& ex)
 {
-    if (pieces != 2 && pieces != 3) return hipErrorInvalidValue;
-    if (!conv3x3_split_supported(N, Cin, H, W, Cout) || ex.bn_part) return hipErrorInvalidValue;
+    // plan.  The walk variables are read at every launch (a getenv costs 0.1 us): tests and A/B runs flip them inside one process
+    const char* env_walk = getenv("SSTEM_SPLIT_WALK");
+    const char* env_walk_min = getenv("SSTEM_SPLIT_WALK_MIN_WGS");
+    const char* env_ctw = ex.out_blocked == 2 ? getenv("SSTEM_SPLIT_WALK_CT") : nullptr;
+    const SplitPlan p = split_forward_plan(N, Cin, H, W, Cout, pieces, ex, out != nullptr, (reinterpret_cast<uintptr_t>(in) & 15) == 0,
+                                           workspace_floats, env_walk ? atoi(env_walk) : 8, env_walk_min ? atoi(env_walk_min) : 2048,
+                                           env_ctw ? atoi(env_ctw) : 8);
+    if (!p.ok) return hipErrorInvalidValue;
     const bool f16 = ex.f16 != 0;
-    if (f16 && !conv3x3_split_f16_supported(N, Cin, H, W, Cout)) return hipErrorInvalidValue;
-    if (f16 && (pieces != 2 || !ex.in_amax)) return hipErrorInvalidValue;
-    if (f16 && (ex.in_mask || ex.out_mask) && (ex.out_blocked || ex.pool_out || ex.out_img_stride)) return hipErrorInvalidValue;   // masks: plain NCHW stores
-    if ((ex.out_blocked == 1 && ex.residual) || (ex.out_blocked && ex.out_mask)) return hipErrorInvalidValue;
-    const SplitGeom geo = split_geom(N, Cin, H, W, Cout);
-    const int CO = geo.CO, ncb = geo.ncb, nchunks = (Cin + SKC - 1) / SKC, COP = split_cop(Cout);
-    const int64_t welems = packed_split_elems(Cin, Cout, pieces) + (f16 ? F16_HDR_ELEMS + 2 * F16_TAIL_FLOATS : 0);
+    const int nchunks = (Cin + SKC - 1) / SKC, COP = split_cop(Cout);
+    const int64_t welems = split_workspace_elems(Cin, Cout, pieces, f16);
     __bf16* wp = reinterpret_cast<__bf16*>(workspace);
     const bool prepacked = (w_transposed_flipped & 2) != 0;
     w_transposed_flipped &= 1;
+    // pack
     hipError_t e = hipSuccess;
     if (f16) {     // [header 16 B][packed image][amax word of the weights]
         const int64_t pelems = packed_split_elems(Cin, Cout, 2);
@@ -1246,174 +1307,55 @@ hipError_t launch_conv3x3_split_mfma(const float* in, const float* w, const floa
             if (e != hipSuccess) return e;
             e = launch_amax(w, (int64_t)Cin * Cout * 9, w_word, s);
             if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(pack_weights_3x3_split_f16, dim3(grid_1d_s(pelems, 256)), dim3(256), 0, s, w, wp, w_word, Cin, Cout, COP, nchunks,
-                               pelems, w_transposed_flipped);
-            e = hipGetLastError();
+            e = launch_kernel<pack_weights_3x3_split_f16>(dim3(grid_1d_s(pelems, 256)), dim3(256), 0, s, w, wp, w_word, Cin, Cout, COP, nchunks,
+                                                          pelems, w_transposed_flipped);
             if (e != hipSuccess) return e;
         }
     } else if (!prepacked) {
-        if (pieces == 3)
-            hipLaunchKernelGGL(pack_weights_3x3_split_both<3>, dim3(grid_1d_s(welems, 256)), dim3(256), 0, s, w, wp, (__bf16*)nullptr, Cin, Cout,
-                               COP, nchunks, welems, 0, 0, (int64_t)0, w_transposed_flipped);
-        else
-            hipLaunchKernelGGL(pack_weights_3x3_split_both<2>, dim3(grid_1d_s(welems, 256)), dim3(256), 0, s, w, wp, (__bf16*)nullptr, Cin, Cout,
-                               COP, nchunks, welems, 0, 0, (int64_t)0, w_transposed_flipped);
-        e = hipGetLastError();
+        e = with_flags([&](auto p3) {
+            return launch_kernel<pack_weights_3x3_split_both<p3() ? 3 : 2>>(dim3(grid_1d_s(welems, 256)), dim3(256), 0, s, w, wp, (__bf16*)nullptr, Cin,
+                                                                            Cout, COP, nchunks, welems, 0, 0, (int64_t)0, w_transposed_flipped);
+        }, pieces == 3);
         if (e != hipSuccess) return e;
     }
-    const bool ct = ex.out_blocked == 2;                     // the sub-pixel form of a ConvTranspose2d(k3, s2, p1, op1): see the kernel
-    if (ct && (!f16 || Cout % 128 != 0 || Cin % SKC != 0 || W % 4 != 0)) return hipErrorInvalidValue;
-    const int64_t out_img = ex.out_img_stride;               // floats between the images of `out` (0: back to back)
-    // a pooled copy: whole tiles only (H % 8 == 0, W % 32 == 0), the fp16 id, plain NCHW store without residual, never split over K
-    if (ex.pool_out && (!f16 || ex.out_blocked || ex.residual || H % 8 != 0 || W % 32 != 0 || ex.pool_kind < 1 || ex.pool_kind > 2 ||
-                        (int64_t)Cout * H * W * 4 >= ((int64_t)1 << 32)))      // (whole tiles of one image below 4 GiB: the buffer-resource store path)
-        return hipErrorInvalidValue;
-    if (!out && !ex.pool_out) return hipErrorInvalidValue;   // no full-resolution output: only next to a pooled copy
-    int ksplit = (ex.out_blocked || out_img || ex.pool_out) ? 1 : geo.ksplit;      // a blocked / shuffled / strided / pooled store is the launch's own
-    const int64_t out_elems = (int64_t)N * Cout * H * W;
-    if (ksplit > 1 && workspace_floats < welems / 2 + (int64_t)ksplit * out_elems) ksplit = 1;
+    // dispatch.  One argument list for every instance: a launch split over K leaves the mask and the output's bound to its slice-sum
+    // launch; the bf16-piece instances take no bounds; only the fp16 per-tile-store instances store a pooled copy
     float* slab = workspace + welems / 2;
-    static const bool novec = [] { const char* e = getenv("SSTEM_BF16_NOVEC"); return e && atoi(e) != 0; }();
-    // 16-byte staging; fp16 pieces: eight channel planes stay below 2^31 bytes (the staging loads' buffer resource, lanes outside at 2^31)
-    const bool vec = !novec && W % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (!f16 || (int64_t)H * W * 32 < ((int64_t)1 << 31));
-    const bool w16 = vec && split_wt16(W);
-    const int tw = w16 ? 16 : STW, th = w16 ? 16 : STH;
-    const dim3 grid((W + tw - 1) / tw, (H + th - 1) / th, (unsigned)(N * ncb * ksplit));
-    if (!vec && (int64_t)Cin * H * W * 4 >= (int64_t)S_OOB) return hipErrorInvalidValue;
-    static const int remap_knob = [] { const char* e = getenv("SSTEM_XCD_REMAP"); return e ? atoi(e) : 1; }();
-    const int remap = (remap_knob && (int64_t)grid.x * grid.y * grid.z < ((int64_t)1 << 31)) ? 1 : 0;
-    const bool masked = ex.in_mask != nullptr || ex.out_mask != nullptr;
-    uint8_t* kernel_out_mask = ksplit > 1 ? nullptr : ex.out_mask;          // a launch split over K leaves the mask to its slice-sum launch
-    float* kernel_out_amax = ksplit > 1 ? nullptr : ex.out_amax;            // ... and the output's bound as well
+    const int remap = (int64_t)p.grid.x * p.grid.y * p.grid.z < ((int64_t)1 << 31) ? 1 : 0;      // 32-bit linear tile ids in the kernel
+    uint8_t* kernel_out_mask = p.ksplit > 1 ? nullptr : ex.out_mask;
+    float* kernel_out_amax = p.ksplit > 1 ? nullptr : ex.out_amax;
+    const float* in_amax = f16 ? ex.in_amax : nullptr;
+    const float* w_bound = f16 ? reinterpret_cast<const float*>(wp) : nullptr;
+    const __bf16* wimg = f16 ? wp + F16_HDR_ELEMS : wp;
+    const int pool_kind = (f16 && !p.ct) ? ex.pool_kind : 0;
+    const int walk = p.ct ? p.ctwalk : p.walk;               // the tile-walking stream (DEEP): the grid's y extent shrinks accordingly
+    const dim3 grid(p.grid.x, walk ? (p.grid.y + walk - 1) / walk : p.grid.y, p.grid.z);
     int lds_bytes = 2 * pieces * SIN_BYTES + 256 * 16 + 64 * 12;      // piece images, parking slots, the per-channel table of the store phase
 #if SSTEM_SPLIT_ABLATE
     if (const char* pad = getenv("SSTEM_SPLIT_LDS_PAD")) lds_bytes += atoi(pad);          // occupancy experiments
 #endif
-    const bool tail = split_tail_chunk(Cin, pieces, f16);      // the packing's own rule
-    const float* w_bound = f16 ? reinterpret_cast<const float*>(wp) : nullptr;
-    const __bf16* wimg = f16 ? wp + F16_HDR_ELEMS : wp;
-#define SSTEM_SPLIT_FWD_T(A, B, PP, V, M, T, TL)                                                                                  \
-    do {                                                                                                                          \
-        static bool done[64] = {};                                                                                                \
-        e = wgrad_split_lds(reinterpret_cast<const void*>(conv3x3_split_mfma<A, B, PP, V, M, T, TL>), lds_bytes, done);           \
-        if (e != hipSuccess) return e;                                                                                            \
-        hipLaunchKernelGGL((conv3x3_split_mfma<A, B, PP, V, M, T, TL>), grid, dim3(256), lds_bytes, s, in, wimg, bias, scale, shift, out, N, Cin, \
-                           H, W, Cout, nchunks, ncb, act, slope, ksplit, slab, remap, ex.residual, ex.res_scale, COP, ex.in_mask,  \
-                           kernel_out_mask, nullptr, nullptr, kernel_out_amax, ex.out_blocked, 1, out_img);                       \
-    } while (0)
-#define SSTEM_SPLIT_F16_TM(A, B, V, T, TL, M)                                                                                     \
-    do {                                                                                                                          \
-        static bool done[64] = {};                                                                                                \
-        e = wgrad_split_lds(reinterpret_cast<const void*>(conv3x3_split_mfma<A, B, 2, V, M, T, TL, true>), lds_bytes, done);      \
-        if (e != hipSuccess) return e;                                                                                            \
-        hipLaunchKernelGGL((conv3x3_split_mfma<A, B, 2, V, M, T, TL, true>), grid, dim3(256), lds_bytes, s, in, wimg, bias, scale, shift, \
-                           out, N, Cin, H, W, Cout, nchunks, ncb, act, slope, ksplit, slab, remap, ex.residual, ex.res_scale, COP,  \
-                           ex.in_mask, kernel_out_mask, ex.in_amax, w_bound, kernel_out_amax, ex.out_blocked, 1, out_img, ex.pool_out, ex.pool_kind); \
-    } while (0)
-    // (masked fp16 instances -- recorded launches, round 5 -- exist for the 16-byte staging path; the dword path keeps bf16 pieces)
-#define SSTEM_SPLIT_F16_T(A, B, V, T, TL)                                                                                         \
-    do { if (masked) { if constexpr (V) SSTEM_SPLIT_F16_TM(A, B, V, T, TL, true); else return hipErrorInvalidValue; }             \
-         else SSTEM_SPLIT_F16_TM(A, B, V, T, TL, false); } while (0)
-#define SSTEM_SPLIT_F16(A, B, V, T)                                                                                               \
-    do { if (tail) SSTEM_SPLIT_F16_T(A, B, V, T, true); else SSTEM_SPLIT_F16_T(A, B, V, T, false); } while (0)
-    // the tile-walking stream (DEEP): `walk` tiles down the image per workgroup, the grid's y extent shrinks accordingly
-#define SSTEM_SPLIT_F16_DEEP(A, B)                                                                                                \
-    do {                                                                                                                          \
-        static bool done[64] = {};                                                                                                \
-        e = wgrad_split_lds(reinterpret_cast<const void*>(conv3x3_split_mfma<A, B, 2, true, false, 32, false, true, true>), lds_bytes, done); \
-        if (e != hipSuccess) return e;                                                                                            \
-        const dim3 gridw(grid.x, (grid.y + walk - 1) / walk, grid.z);                                                             \
-        hipLaunchKernelGGL((conv3x3_split_mfma<A, B, 2, true, false, 32, false, true, true>), gridw, dim3(256), lds_bytes, s, in, wimg, bias, scale, \
-                           shift, out, N, Cin, H, W, Cout, nchunks, ncb, act, slope, 1, slab, remap, ex.residual, ex.res_scale, COP, \
-                           nullptr, nullptr, ex.in_amax, w_bound, kernel_out_amax, ex.out_blocked, walk, out_img, ex.pool_out, ex.pool_kind); \
-    } while (0)
-    // which launches walk: fp16 pieces, 16-byte staging, 32-wide tiles, no tap-row chunk, no K slices, and enough workgroups left to
-    // fill the chip several times over (SSTEM_SPLIT_WALK: 0 = never, n = tiles per workgroup)
-    // (read at every launch -- a getenv costs 0.1 us --: tests and A/B runs flip them inside one process; SSTEM_SPLIT_WALK_MIN_WGS: the
-    // smallest grid a walking launch may be left with)
-    const char* env_walk = getenv("SSTEM_SPLIT_WALK");
-    const char* env_walk_min = getenv("SSTEM_SPLIT_WALK_MIN_WGS");
-    const int walk_knob = env_walk ? atoi(env_walk) : 8;
-    const int64_t walk_min_wgs = env_walk_min ? atoi(env_walk_min) : 2048;
-    int walk = 0;
-    // (the 64-channel-block instance does not walk: its second staging set spills -- 256 VGPRs + 59 -- and it is power-bound: measured 3 % slower)
-    if (f16 && vec && !w16 && !tail && ksplit == 1 && walk_knob > 0 && CO == 32 && !masked) {
-        walk = walk_knob;
-        while (walk > 1 && (int64_t)grid.x * ((grid.y + walk - 1) / walk) * grid.z < walk_min_wgs) walk >>= 1;
-        if (walk < 2) walk = 0;
-    }
-#define SSTEM_SPLIT_FWD(A, B, PP, V, M, T)                                                                                        \
-    do {                                                                                                                          \
-        if constexpr (PP == 3) { if (tail) { SSTEM_SPLIT_FWD_T(A, B, PP, V, M, T, true); break; } }                               \
-        SSTEM_SPLIT_FWD_T(A, B, PP, V, M, T, false);                                                                              \
-    } while (0)
-#define SSTEM_SPLIT_PV(A, B, PP, V)                                                                                               \
-    do {                                                                                                                          \
-        if constexpr (V) {                                                                                                        \
-            if (w16) { if (masked) SSTEM_SPLIT_FWD(A, B, PP, true, true, 16); else SSTEM_SPLIT_FWD(A, B, PP, true, false, 16); break; } \
-        }                                                                                                                         \
-        if (masked) SSTEM_SPLIT_FWD(A, B, PP, V, true, 32); else SSTEM_SPLIT_FWD(A, B, PP, V, false, 32);                        \
-    } while (0)
-#define SSTEM_SPLIT_SHAPE(A, B)                                                                          \
-    do {                                                                                                 \
-        if (pieces == 3) { if (vec) SSTEM_SPLIT_PV(A, B, 3, true); else SSTEM_SPLIT_PV(A, B, 3, false); } \
-        else { if (vec) SSTEM_SPLIT_PV(A, B, 2, true); else SSTEM_SPLIT_PV(A, B, 2, false); }           \
-    } while (0)
-#define SSTEM_SPLIT_F16_CT()                                                                                                       \
-    do {                                                                                                                          \
-        static bool done[64] = {};                                                                                                \
-        e = wgrad_split_lds(reinterpret_cast<const void*>(conv3x3_split_mfma<2, 2, 2, true, false, 32, false, true, false, true>), lds_bytes, done); \
-        if (e != hipSuccess) return e;                                                                                            \
-        hipLaunchKernelGGL((conv3x3_split_mfma<2, 2, 2, true, false, 32, false, true, false, true>), grid, dim3(256), lds_bytes, s, in, wimg, bias, \
-                           scale, shift, out, N, Cin, H, W, Cout, nchunks, ncb, act, slope, 1, slab, remap, ex.residual, ex.res_scale, COP, \
-                           nullptr, nullptr, ex.in_amax, w_bound, kernel_out_amax, 2, 1, out_img);                                \
-    } while (0)
-    // ... and its tile-walking form (4 of 9 taps: 12 MFMAs per MFMA row, chunk and piece -- steps as short as the 32-channel block's)
-#define SSTEM_SPLIT_F16_CT_DEEP()                                                                                                  \
-    do {                                                                                                                          \
-        static bool done[64] = {};                                                                                                \
-        e = wgrad_split_lds(reinterpret_cast<const void*>(conv3x3_split_mfma<2, 2, 2, true, false, 32, false, true, true, true>), lds_bytes, done); \
-        if (e != hipSuccess) return e;                                                                                            \
-        const dim3 gridw(grid.x, (grid.y + ctwalk - 1) / ctwalk, grid.z);                                                         \
-        hipLaunchKernelGGL((conv3x3_split_mfma<2, 2, 2, true, false, 32, false, true, true, true>), gridw, dim3(256), lds_bytes, s, in, wimg, bias, \
-                           scale, shift, out, N, Cin, H, W, Cout, nchunks, ncb, act, slope, 1, slab, remap, ex.residual, ex.res_scale, COP, \
-                           nullptr, nullptr, ex.in_amax, w_bound, kernel_out_amax, 2, ctwalk, out_img);                           \
-    } while (0)
-    if (ct) {
-        if (!vec || w16 || tail || CO != 64) return hipErrorInvalidValue;
-        const char* env_ctw = getenv("SSTEM_SPLIT_WALK_CT");             // tiles a sub-pixel ConvTranspose workgroup walks (0 = per-tile kernel)
-        int ctwalk = env_ctw ? atoi(env_ctw) : 8;
-        while (ctwalk > 1 && (int64_t)grid.x * ((grid.y + ctwalk - 1) / ctwalk) * grid.z < 2048) ctwalk >>= 1;
-        if (ctwalk >= 2) SSTEM_SPLIT_F16_CT_DEEP(); else SSTEM_SPLIT_F16_CT();
-        return hipGetLastError();
-    }
-#undef SSTEM_SPLIT_F16_CT_DEEP
-#undef SSTEM_SPLIT_F16_CT
-#if SSTEM_SPLIT_DEV      // developer builds (minutes of compile time less): only the 16-byte-staging fp16 instances of 32-wide tiles
-    if (!f16 || w16 || !vec) return hipErrorInvalidValue;
-    if (walk) SSTEM_SPLIT_F16_DEEP(1, 4);
-    else if (CO == 64) SSTEM_SPLIT_F16(2, 2, true, 32); else SSTEM_SPLIT_F16(1, 4, true, 32);
-#else
-    if (walk) SSTEM_SPLIT_F16_DEEP(1, 4);
-    else if (f16) {
-        if (CO == 64) { if (w16) SSTEM_SPLIT_F16(2, 2, true, 16); else if (vec) SSTEM_SPLIT_F16(2, 2, true, 32); else SSTEM_SPLIT_F16(2, 2, false, 32); }
-        else { if (w16) SSTEM_SPLIT_F16(1, 4, true, 16); else if (vec) SSTEM_SPLIT_F16(1, 4, true, 32); else SSTEM_SPLIT_F16(1, 4, false, 32); }
-    } else if (CO == 64) SSTEM_SPLIT_SHAPE(2, 2); else SSTEM_SPLIT_SHAPE(1, 4);
-#endif
-#undef SSTEM_SPLIT_F16_DEEP
-#undef SSTEM_SPLIT_F16
-#undef SSTEM_SPLIT_F16_T
-#undef SSTEM_SPLIT_F16_TM
-#undef SSTEM_SPLIT_SHAPE
-#undef SSTEM_SPLIT_PV
-#undef SSTEM_SPLIT_FWD
-#undef SSTEM_SPLIT_FWD_T
-    e = hipGetLastError();
-    if (e != hipSuccess || ksplit == 1) return e;
-    const int eg = grid_1d_s(out_elems, 256);
-    hipLaunchKernelGGL(conv3x3_split_splitk_epilogue, dim3(eg), dim3(256), 0, s, slab, bias, scale, shift, out,
-                       out_elems, (int64_t)H * W, Cout, ksplit, act, slope, ex.residual, ex.res_scale, ex.out_mask, ex.out_amax);
-    return hipGetLastError();
+    e = with_flags([&](auto co64, auto p3, auto h, auto v, auto m, auto t16, auto tl, auto deep, auto ct) -> hipError_t {
+        // the instances that exist: 16-wide tiles and masked fp16 pieces need the 16-byte staging, a tap-row chunk three pieces or fp16
+        // ones; the walking and the ConvTranspose instances are plain fp16 ones, of the 32- and of the 64-channel block
+        constexpr bool plain_f16 = h() && !p3() && v() && !m() && !t16() && !tl();
+        constexpr bool exists = ct()   ? plain_f16 && co64()
+                                : deep() ? plain_f16 && !co64()
+                                : h()    ? !p3() && (v() || (!t16() && !m()))
+                                         : (v() || !t16()) && (p3() || !tl());
+        if constexpr (!exists || (SSTEM_SPLIT_DEV && !ct() && !(h() && v() && !t16()))) {
+            return hipErrorInvalidValue;           // (the plan refuses these)
+        } else {
+            return launch_kernel<conv3x3_split_mfma<co64() ? 2 : 1, co64() ? 2 : 4, p3() ? 3 : 2, v(), m(), t16() ? 16 : 32, tl(), h(), deep(), ct()>>(
+                grid, dim3(256), lds_bytes, s, in, wimg, bias, scale, shift, out, N, Cin, H, W, Cout, nchunks, p.ncb, act, slope, p.ksplit, slab,
+                remap, ex.residual, ex.res_scale, COP, ex.in_mask, kernel_out_mask, in_amax, w_bound, kernel_out_amax, ex.out_blocked,
+                walk ? walk : 1, ex.out_img_stride, ex.pool_out, pool_kind);
+        }
+    }, p.CO == 64, pieces == 3, f16, p.vec, p.masked, p.w16, p.tail, walk > 0, p.ct);
+    if (e != hipSuccess || p.ksplit == 1) return e;
+    // epilogue: the slice sum
+    return launch_kernel<conv3x3_split_splitk_epilogue>(dim3(grid_1d_s((int64_t)N * Cout * H * W, 256)), dim3(256), 0, s, slab, bias, scale, shift,
+                                                        out, (int64_t)N * Cout * H * W, (int64_t)H * W, Cout, p.ksplit, act, slope, ex.residual,
+                                                        ex.res_scale, ex.out_mask, ex.out_amax);
 }
 
 }  // namespace sstem

@@ -7,6 +7,7 @@
 
 #include "conv_kernels.h"
 #include "conv_split_common.h"
+#include "conv_launch.h"
 
 #ifndef SSTEM_SPLIT_DEV
 #define SSTEM_SPLIT_DEV 0
@@ -515,19 +516,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_split_mfma(
 struct WgradSplitPlan { int CinP, CoutP, ksplit, tx, ty; };
 static WgradSplitPlan wgrad_split_plan(int N, int Cin, int H, int W, int Cout)
 {
-    static const int target = [] { const char* e = getenv("SSTEM_WGRAD_SPLIT_TARGET"); return e ? atoi(e) : 256; }();
-    static const int min_tiles = [] { const char* e = getenv("SSTEM_WGRAD_SPLIT_MIN_TILES"); return e ? atoi(e) : 2; }();
     WgradSplitPlan p;
     p.CinP = (Cin + 63) / 64 * 64;
     p.CoutP = (Cout + 63) / 64 * 64;
     p.tx = (W + STW - 1) / STW;
     p.ty = (H + 1) / 2;
-    const int64_t ntiles = (int64_t)N * p.tx * p.ty;
-    const int blocks = (p.CinP / 64) * (p.CoutP / 64);
-    int64_t k = (target + blocks - 1) / blocks;
-    if (k > ntiles / min_tiles) k = ntiles / min_tiles;
-    if (k < 1) k = 1;
-    p.ksplit = (int)k;
+    p.ksplit = wgrad_slabs(256, (p.CinP / 64) * (p.CoutP / 64), (int64_t)N * p.tx * p.ty, 2);
     return p;
 }
 
@@ -547,53 +541,31 @@ hipError_t launch_conv3x3_wgrad_split_mfma(const float* in, const float* g, floa
     const bool f16 = in_amax != nullptr || g_amax != nullptr;            // both words: the two-piece fp16 form
     if (f16 && (pieces != 2 || !in_amax || !g_amax)) return hipErrorInvalidValue;
     if (!conv3x3_wgrad_split_supported(N, Cin, H, W, Cout)) return hipErrorInvalidValue;
-    const WgradSplitPlan p = wgrad_split_plan(N, Cin, H, W, Cout);
-    float* bias_slab = gb ? workspace + (int64_t)p.ksplit * wgrad_slab_floats(p.CoutP, p.CinP) : nullptr;
-    const int blocks = (p.CinP / 64) * (p.CoutP / 64);
-    static const bool novec = [] { const char* e = getenv("SSTEM_BF16_NOVEC"); return e && atoi(e) != 0; }();
-    static const int runs = [] { const char* e = getenv("SSTEM_WGRAD_RUNS"); return e ? atoi(e) : 2; }();
-    const bool vec = !novec && W % 4 == 0 && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(g)) & 15) == 0;
-    const int lds = pieces * (SWG_BYTES + SWI_BYTES);
-    // the fp16 form with two buffer sets and the waves of a SIMD half a tile apart (SSTEM_WGRAD_PINGPONG=0: one set, two barriers)
-    const char* env_pp = getenv("SSTEM_WGRAD_PINGPONG");
-    const bool pingpong = env_pp ? atoi(env_pp) != 0 : true;
-    hipError_t e;
-#define SSTEM_WGRAD_SPLIT(PP, V, M)                                                                                                \
-    do {                                                                                                                           \
-        static bool done[64] = {};                                                                                                 \
-        e = wgrad_split_lds(reinterpret_cast<const void*>(conv3x3_wgrad_split_mfma<PP, V, M>), lds, done);                         \
-        if (e != hipSuccess) return e;                                                                                             \
-        hipLaunchKernelGGL((conv3x3_wgrad_split_mfma<PP, V, M>), dim3((unsigned)(blocks * p.ksplit)), dim3(512), lds, s, in, g, workspace, \
-                           N, Cin, H, W, Cout, p.CinP, p.CoutP, p.ksplit, p.tx, p.ty, bias_slab, runs, g_mask);                    \
-    } while (0)
-#define SSTEM_WGRAD_SPLIT_F16_PP(V, M, PP)                                                                                         \
-    do {                                                                                                                           \
-        static bool done[64] = {};                                                                                                 \
-        const int ldsp = (PP ? 2 : 1) * lds;                                                                                       \
-        e = wgrad_split_lds(reinterpret_cast<const void*>(conv3x3_wgrad_split_mfma<2, V, M, true, PP>), ldsp, done);               \
-        if (e != hipSuccess) return e;                                                                                             \
-        hipLaunchKernelGGL((conv3x3_wgrad_split_mfma<2, V, M, true, PP>), dim3((unsigned)(blocks * p.ksplit)), dim3(512), ldsp, s, in, g, \
-                           workspace, N, Cin, H, W, Cout, p.CinP, p.CoutP, p.ksplit, p.tx, p.ty, bias_slab, runs, g_mask, in_amax, g_amax); \
-    } while (0)
-#define SSTEM_WGRAD_SPLIT_F16(V, M) do { if (pingpong) SSTEM_WGRAD_SPLIT_F16_PP(V, M, true); else SSTEM_WGRAD_SPLIT_F16_PP(V, M, false); } while (0)
-#define SSTEM_WGRAD_SPLIT_PV(PP, V) do { if (g_mask) SSTEM_WGRAD_SPLIT(PP, V, true); else SSTEM_WGRAD_SPLIT(PP, V, false); } while (0)
 #if SSTEM_SPLIT_DEV
     return hipErrorInvalidValue;
 #else
-    if (f16) {
-        if (vec) { if (g_mask) SSTEM_WGRAD_SPLIT_F16(true, true); else SSTEM_WGRAD_SPLIT_F16(true, false); }
-        else { if (g_mask) SSTEM_WGRAD_SPLIT_F16(false, true); else SSTEM_WGRAD_SPLIT_F16(false, false); }
-    }
-    else if (pieces == 3) { if (vec) SSTEM_WGRAD_SPLIT_PV(3, true); else SSTEM_WGRAD_SPLIT_PV(3, false); }
-    else { if (vec) SSTEM_WGRAD_SPLIT_PV(2, true); else SSTEM_WGRAD_SPLIT_PV(2, false); }
-#endif
-#undef SSTEM_WGRAD_SPLIT_PV
-#undef SSTEM_WGRAD_SPLIT_F16
-#undef SSTEM_WGRAD_SPLIT_F16_PP
-#undef SSTEM_WGRAD_SPLIT
-    e = hipGetLastError();
+    const WgradSplitPlan p = wgrad_split_plan(N, Cin, H, W, Cout);
+    float* bias_slab = gb ? workspace + (int64_t)p.ksplit * wgrad_slab_floats(p.CoutP, p.CinP) : nullptr;
+    const int blocks = (p.CinP / 64) * (p.CoutP / 64);
+    const int runs = 2;                  // a workgroup's pixel tiles: runs down a column strip (0: strided, 1: runs along x)
+    const bool vec = W % 4 == 0 && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(g)) & 15) == 0;
+    // the fp16 form with two buffer sets and the waves of a SIMD half a tile apart (SSTEM_WGRAD_PINGPONG=0: one set, two barriers)
+    const char* env_pp = getenv("SSTEM_WGRAD_PINGPONG");
+    const bool pingpong = f16 && (env_pp ? atoi(env_pp) != 0 : true);
+    const int lds = (pingpong ? 2 : 1) * pieces * (SWG_BYTES + SWI_BYTES);
+    // dispatch: piece format x staging x mask; two buffer sets exist for the fp16 pieces only
+    const hipError_t e = with_flags([&](auto p3, auto f, auto v, auto m, auto pp) -> hipError_t {
+        if constexpr ((p3() && f()) || (pp() && !f())) {
+            return hipErrorInvalidValue;           // (refused above / pingpong is false)
+        } else {
+            return launch_kernel<conv3x3_wgrad_split_mfma<p3() ? 3 : 2, v(), m(), f(), pp()>>(
+                dim3((unsigned)(blocks * p.ksplit)), dim3(512), lds, s, in, g, workspace, N, Cin, H, W, Cout, p.CinP, p.CoutP, p.ksplit, p.tx, p.ty,
+                bias_slab, runs, g_mask, in_amax, g_amax);
+        }
+    }, pieces == 3, f16, vec, g_mask != nullptr, pingpong);
     if (e != hipSuccess) return e;
     return launch_conv3x3_wgrad_reduce(workspace, gw, Cin, Cout, p.CinP, p.CoutP, p.ksplit, bias_slab, gb, p.ksplit, s, accumulate);
+#endif
 }
 
 }  // namespace sstem

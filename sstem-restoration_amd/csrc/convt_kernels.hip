@@ -25,6 +25,7 @@
 #include <stdlib.h>
 
 #include "conv_kernels.h"
+#include "conv_launch.h"
 
 namespace sstem {
 
@@ -608,15 +609,8 @@ __global__ __launch_bounds__(64 * TRED_KG) void convT_wgrad_reduce(const float* 
                             (int)(blockDim.x >> 6), part);
 }
 
-// K slices of the reduction channels on small grids (as conv3x3_ksplit)
-int convT_ksplit(int64_t wgs, int nchunks)
-{
-    static const bool off = [] { const char* e = getenv("SSTEM_CONV_KSPLIT"); return e && atoi(e) == 0; }();
-    if (off) return 1;
-    int ks = 1;
-    while (wgs * ks < 512 && ks < 8 && nchunks % (ks * 2) == 0 && nchunks / (ks * 2) >= 2) ks *= 2;
-    return ks;
-}
+// K slices of the reduction channels on small grids (conv_ksplit)
+int convT_ksplit(int64_t wgs, int nchunks) { return conv_ksplit(wgs, nchunks, 512, 2); }
 
 struct WgPlan { int CinP, CoutP, ksplit, tx, ty; };
 WgPlan convT_wgrad_plan(int N, int Cin, int H, int W, int Cout)
@@ -626,12 +620,8 @@ WgPlan convT_wgrad_plan(int N, int Cin, int H, int W, int Cout)
     p.CoutP = (Cout + WGT_CO - 1) / WGT_CO * WGT_CO;
     p.tx = (W + TW - 1) / TW;
     p.ty = (H + 1) / 2;
-    const int64_t ntiles = (int64_t)N * p.tx * p.ty;
-    const int blocks = (p.CinP / WGT_CI) * (p.CoutP / WGT_CO);
-    int64_t k = (256 + blocks - 1) / blocks;          // ~256 workgroups of 8 waves (one per CU); at least two tiles each (the prefetch)
-    if (k > ntiles / 2) k = ntiles / 2;
-    if (k < 1) k = 1;
-    p.ksplit = (int)k;
+    // ~256 workgroups of 8 waves (one per CU); at least two tiles each (the prefetch)
+    p.ksplit = wgrad_slabs(256, (p.CinP / WGT_CI) * (p.CoutP / WGT_CO), (int64_t)N * p.tx * p.ty, 2);
     return p;
 }
 
@@ -675,14 +665,9 @@ hipError_t launch_convT3x3s2_mfma(const float* in, const float* w, const float* 
                                   float* out, float* workspace, int64_t workspace_floats, int N, int Cin, int H, int W, int Cout,
                                   int act, float slope, int prepacked, hipStream_t s, const ConvExtra& ex_in)
 {
+    // plan
     const int ncb = (Cout + CO - 1) / CO, nchunks = (Cin + KC - 1) / KC;
     const int64_t wtotal = (int64_t)ncb * nchunks * KK * CO;
-    hipError_t e;
-    if (!prepacked) {
-        hipLaunchKernelGGL(convT_pack_weights, dim3(grid_1d(wtotal, 256)), dim3(256), 0, s, w, workspace, Cin, Cout, nchunks, ncb, 1);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
     const dim3 tiles((W + TW - 1) / TW, (H + TH - 1) / TH);
     int ksplit = convT_ksplit((int64_t)tiles.x * tiles.y * N * ncb, nchunks);
     const int64_t out_elems = (int64_t)N * Cout * 4 * H * W;
@@ -692,43 +677,40 @@ hipError_t launch_convT3x3s2_mfma(const float* in, const float* w, const float* 
     ex.bn_tiles = (int)(N * tiles.x * tiles.y);
     if ((int64_t)N * ncb * ksplit > 65535) return hipErrorInvalidValue;
     float* slab = workspace + wtotal;
-    const size_t lds_bytes = 2 * (size_t)F_BUF * sizeof(float);
-    auto k = convT3x3s2_mfma;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(tiles.x, tiles.y, (unsigned)(N * ncb * ksplit)), dim3(256), lds_bytes, s, in, workspace, bias, scale,
-                       shift, out, N, Cin, H, W, Cout, nchunks, ncb, act, slope, ksplit, slab, ex);
-    e = hipGetLastError();
+    // pack
+    hipError_t e;
+    if (!prepacked) {
+        e = launch_kernel<convT_pack_weights>(dim3(grid_1d(wtotal, 256)), dim3(256), 0, s, w, workspace, Cin, Cout, nchunks, ncb, 1);
+        if (e != hipSuccess) return e;
+    }
+    e = launch_kernel<convT3x3s2_mfma>(dim3(tiles.x, tiles.y, (unsigned)(N * ncb * ksplit)), dim3(256), 2 * (size_t)F_BUF * sizeof(float), s, in,
+                                       workspace, bias, scale, shift, out, N, Cin, H, W, Cout, nchunks, ncb, act, slope, ksplit, slab, ex);
     if (e != hipSuccess || ksplit == 1) return e;
-    hipLaunchKernelGGL(convT_splitk_epilogue, dim3(grid_1d(out_elems, 256)), dim3(256), 0, s, slab, bias, scale, shift, out, out_elems,
-                       (int64_t)4 * H * W, Cout, ksplit, act, slope, ex.residual, ex.res_scale);
-    return hipGetLastError();
+    // epilogue: the slice sum
+    return launch_kernel<convT_splitk_epilogue>(dim3(grid_1d(out_elems, 256)), dim3(256), 0, s, slab, bias, scale, shift, out, out_elems,
+                                                (int64_t)4 * H * W, Cout, ksplit, act, slope, ex.residual, ex.res_scale);
 }
 
 hipError_t launch_convT3x3s2_dgrad_mfma(const float* g, const float* w, float* gin, float* workspace, int64_t workspace_floats,
                                         int N, int Cin, int H, int W, int Cout, hipStream_t s)
 {
+    // plan
     const int ncb = (Cin + CO - 1) / CO, nchunks = (Cout + KC - 1) / KC;
     const int64_t wtotal = (int64_t)ncb * nchunks * KK * CO;
-    hipLaunchKernelGGL(convT_pack_weights, dim3(grid_1d(wtotal, 256)), dim3(256), 0, s, w, workspace, Cin, Cout, nchunks, ncb, 0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
     const dim3 tiles((W + TW - 1) / TW, (H + TH - 1) / TH);
     int ksplit = convT_ksplit((int64_t)tiles.x * tiles.y * N * ncb, nchunks);
     const int64_t out_elems = (int64_t)N * Cin * H * W;
     if (ksplit > 1 && workspace_floats < wtotal + (int64_t)ksplit * out_elems) ksplit = 1;
     if ((int64_t)N * ncb * ksplit > 65535) return hipErrorInvalidValue;
     float* slab = workspace + wtotal;
-    const size_t lds_bytes = (size_t)(D_TILE + D_WT) * sizeof(float);
-    auto k = convT3x3s2_dgrad_mfma;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    // pack
+    hipError_t e = launch_kernel<convT_pack_weights>(dim3(grid_1d(wtotal, 256)), dim3(256), 0, s, w, workspace, Cin, Cout, nchunks, ncb, 0);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(tiles.x, tiles.y, (unsigned)(N * ncb * ksplit)), dim3(256), lds_bytes, s, g, workspace, gin, N, Cin, H, W,
-                       Cout, nchunks, ncb, ksplit, slab);
-    e = hipGetLastError();
+    e = launch_kernel<convT3x3s2_dgrad_mfma>(dim3(tiles.x, tiles.y, (unsigned)(N * ncb * ksplit)), dim3(256), (size_t)(D_TILE + D_WT) * sizeof(float),
+                                             s, g, workspace, gin, N, Cin, H, W, Cout, nchunks, ncb, ksplit, slab);
     if (e != hipSuccess || ksplit == 1) return e;
-    hipLaunchKernelGGL(convT_sum_slabs, dim3(grid_1d(out_elems, 256)), dim3(256), 0, s, slab, gin, out_elems, ksplit);
-    return hipGetLastError();
+    // epilogue: the slice sum
+    return launch_kernel<convT_sum_slabs>(dim3(grid_1d(out_elems, 256)), dim3(256), 0, s, slab, gin, out_elems, ksplit);
 }
 
 hipError_t launch_convT3x3s2_wgrad_mfma(const float* in, const float* g, float* gw, float* gb, float* workspace, int N, int Cin,
@@ -738,10 +720,10 @@ hipError_t launch_convT3x3s2_wgrad_mfma(const float* in, const float* g, float* 
     const int64_t slab_floats = (int64_t)p.ksplit * 9 * p.CoutP * p.CinP;
     float* bias_slab = gb ? workspace + slab_floats : nullptr;
     const int blocks = (p.CinP / WGT_CI) * (p.CoutP / WGT_CO);
-    hipLaunchKernelGGL(convT3x3s2_wgrad_mfma, dim3((unsigned)(blocks * p.ksplit)), dim3(WG_T), 0, s, in, g, workspace, N, Cin, H, W, Cout,
-                       p.CinP, p.CoutP, p.ksplit, p.tx, p.ty, bias_slab);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch_kernel<convT3x3s2_wgrad_mfma>(dim3((unsigned)(blocks * p.ksplit)), dim3(WG_T), 0, s, in, g, workspace, N, Cin, H, W, Cout,
+                                                        p.CinP, p.CoutP, p.ksplit, p.tx, p.ty, bias_slab);
     if (e != hipSuccess) return e;
+    // epilogue: the fixed-order sum of the slabs, now or with the other layers' at the end of the backward pass
     int64_t rblocks = (int64_t)9 * p.CoutP * ((p.CinP + 63) / 64);
     if (rblocks > 256 * 64) rblocks = 256 * 64;
     const int bblocks = gb ? (p.CoutP + 63) / 64 : 0;
@@ -751,9 +733,8 @@ hipError_t launch_convT3x3s2_wgrad_mfma(const float* in, const float* g, float* 
                                    groups, 2, accumulate & 1, 0});
         return hipSuccess;
     }
-    hipLaunchKernelGGL(convT_wgrad_reduce, dim3((unsigned)(rblocks + bblocks)), dim3(64 * groups), 0, s, workspace, gw, Cin, Cout, p.CinP,
-                       p.CoutP, p.ksplit, bias_slab, gb, p.ksplit * 16, (int)rblocks, accumulate);
-    return hipGetLastError();
+    return launch_kernel<convT_wgrad_reduce>(dim3((unsigned)(rblocks + bblocks)), dim3(64 * groups), 0, s, workspace, gw, Cin, Cout, p.CinP,
+                                             p.CoutP, p.ksplit, bias_slab, gb, p.ksplit * 16, (int)rblocks, accumulate);
 }
 
 }  // namespace sstem

@@ -38,6 +38,8 @@ def _default_knobs(monkeypatch):
 
 
 # ---- the launchers' dispatch, restated ---------------------------------------------------------------------------------------------------
+# (csrc/conv_split_kernels.hip: split_forward_plan decides -- CO, ncb, ksplit, vec, w16, tail, masked, walk, ct, ctwalk, grid, or a
+# refusal -- and launch_conv3x3_split_mfma dispatches on that struct; fwd_instance below is that plan for 16-byte aligned tensors)
 # conv3x3_split_mfma<A, B, P, V, M, T, TL, F16, DEEP, CT>: CO = 32 (A, B = 1, 4) or 64 (2, 2) output channels per workgroup, P pieces,
 # V 16-byte staging, M masked, T tile width (16: 16 x 16 tiles, 32: 32 x 8), TL tap-row last chunk, DEEP tile-walking, CT sub-pixel store
 Inst = collections.namedtuple("Inst", "CO P V M T TL F16 DEEP CT")

@@ -615,8 +615,8 @@ def test_native_conv_transpose_fused_sequential_block_train_and_eval(fused_bn_st
 # ---- statistics partials from the convolution's own store, residual in the store, gradient sinks ----------------------------------
 @pytest.mark.parametrize("shape", [(16, 6, 64, 64, 32), (2, 32, 37, 45, 70), (2, 256, 16, 16, 128), (1, 8, 5, 7, 3)])
 def test_conv_bn_partials_give_torchs_batch_statistics(shape, fused_bn_stats):
-    """Conv3x3 -> train-mode BatchNorm -> ReLU: the conv launch (unsplit: per-tile partials; split over K: per-chunk partials from
-    the slice-sum kernel under SSTEM_SPLITK_BN=1, by default the BatchNorm's own pass) writes (count, mean, M2) triplets and the
+    """Conv3x3 -> train-mode BatchNorm -> ReLU: the conv launch (unsplit: per-tile partials; a launch split over K writes none and
+    leaves the statistics to the BatchNorm's own pass) writes (count, mean, M2) triplets and the
     BatchNorm forward is ONE pass.  Against float64 torch, and bit for
     bit against the BatchNorm making its own statistics pass is NOT expected (different partial shapes): 2e-5."""
     import copy
