@@ -200,6 +200,34 @@ int64_t sstem_sepconv_forward_bytes_bf16coef(int64_t B, int64_t C, int64_t H, in
 int64_t sstem_sepconv_backward_bytes_bf16coef(int64_t B, int64_t C, int64_t H, int64_t W);
 int64_t sstem_sepconv_interp_apply_bytes_bf16coef(int64_t B, int64_t H, int64_t W, int frame_planes);
 
+/* Input gradient.  THIS LIBRARY'S ADDITION: the reference has no counterpart -- its backward launcher never writes gradInput
+ * (kernel.cu:152-206) and its own gradcheck marks the input requires_grad=False (model_interp.py:109-119, networks.py:131-140).  The
+ * seven-pointer backward entries above keep ignoring grad_input; these entries compute it:
+ *     grad_output g [B,C,H,W], vertical V / horizontal H [B,51,H,W]  ->  grad_input [B,C,H+50,W+50]   (the input is not read)
+ *     gI[b,c,Y,X] = sum_fy sum_fx  g[b,c,Y-fy,X-fx] * V[b,fy,Y-fy,X-fx] * H[b,fx,Y-fy,X-fx]
+ *                   over the (fy,fx) with 0 <= Y-fy < H and 0 <= X-fx < W
+ * Every element is written (no zero-fill needed beforehand), by plain stores: the same bits on every run.
+ * Summation order, the same for every kernel behind these entries: source rows y = Y-fy ASCENDING, source columns x = X-fx ASCENDING
+ * inside a row, one fp32 fmaf chain from +0.  Association of the triple product:  acc = fmaf(V, fl(g * H), acc).  Terms whose source
+ * pixel lies outside the image contribute nothing.
+ * _algo takes the sstem_sepconv_algo ids: DIRECT = one lane per grad_input element (any C); MFMA = the 64 x 64 gather-tile kernel
+ * (4x4x1 fp32 MFMA, C in chunks of three), bit for bit the DIRECT result on finite data (apart from a chain that underflows to -0, which its zero
+ * off-band steps turn into +0); it refuses (SSTEM_ERR_UNSUPPORTED) a grid
+ * past 2^31-1 workgroups and 51*H*W*4 bytes per image of 4 GiB or more, which AUTO hands to DIRECT.
+ * _taps: any filter length, grad_input [B,C,H+taps-1,W+taps-1]; taps == 51 is the _f32 entry, other lengths run on DIRECT.
+ * _bf16coef: bf16 coefficient tensors (as sstem_sepconv_backward_bf16coef), DIRECT kernel: the bits of the _f32 entry on the widened values.
+ * B == 0 or C == 0: successful no-op.  H == 0 or W == 0: grad_input (which still has elements) is set to zero.
+ * bytes: 4*(B*C*H*W + 2*B*51*H*W + B*C*(H+50)*(W+50)) -- the forward's. */
+int sstem_sepconv_backward_input_f32(const float* grad_output, const float* vertical, const float* horizontal, float* grad_input,
+                                     int64_t B, int64_t C, int64_t H, int64_t W, void* stream);
+int sstem_sepconv_backward_input_f32_algo(const float* grad_output, const float* vertical, const float* horizontal, float* grad_input,
+                                          int64_t B, int64_t C, int64_t H, int64_t W, void* stream, int algo);
+int sstem_sepconv_backward_input_taps_f32(const float* grad_output, const float* vertical, const float* horizontal, float* grad_input,
+                                          int64_t B, int64_t C, int64_t H, int64_t W, int taps, void* stream);
+int sstem_sepconv_backward_input_bf16coef(const float* grad_output, const uint16_t* vertical, const uint16_t* horizontal,
+                                          float* grad_input, int64_t B, int64_t C, int64_t H, int64_t W, void* stream);
+int64_t sstem_sepconv_backward_input_bytes(int64_t B, int64_t C, int64_t H, int64_t W);
+
 /* Library / error reporting. */
 int sstem_version(void);                       /* MAJOR*10000 + MINOR*100 + PATCH */
 const char* sstem_status_string(int status);   /* static string, never NULL */

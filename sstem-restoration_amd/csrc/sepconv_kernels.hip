@@ -117,11 +117,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // ---------------------------------------------------------------------------------------------
 // BF: the coefficient tensors are bf16 (widened exactly: the upper half of an fp32); skip_if_gray: the device word of
 // detect_identical_channels -- non-zero means the trusted-gray kernel launched next to this one owns the call.
-template <bool BF> __device__ __forceinline__ float coef_at(const float* t, int64_t i)
-{
-    if constexpr (BF) return __builtin_bit_cast(float, (uint32_t)reinterpret_cast<const uint16_t*>(t)[i] << 16);
-    else return t[i];
-}
+// (coef_at<BF> lives in sepconv_kernels.h: sepconv_gradinput.hip reads coefficients through it too)
 template <bool BF = false>
 __global__ __launch_bounds__(256) void sepconv_fwd_direct(
     const float* __restrict__ in, const float* __restrict__ ver, const float* __restrict__ hor,

@@ -1287,6 +1287,73 @@ int sstem_sepconv_interp_apply_gray_bf16coef(const float* g1, const float* g2, c
     return SSTEM_OK;
 }
 
+// ---- input gradient (the library's addition: the reference's launcher leaves gradInput untouched, kernel.cu:152-206) ---------------
+int64_t sstem_sepconv_backward_input_bytes(int64_t B, int64_t C, int64_t H, int64_t W)
+{
+    return 4 * (B * C * H * W + 2 * B * 51 * H * W + B * C * (H + 50) * (W + 50));
+}
+
+// shared tail of the four entries: taps == 51 unless the _taps entry says otherwise; bf16: coefficient tensors are bf16 (direct kernel)
+static int backward_input(const char* what, const float* grad_output, const float* vertical, const float* horizontal, float* grad_input,
+                          int64_t B, int64_t C, int64_t H, int64_t W, int taps, bool bf16, void* stream, int algo)
+{
+    if (taps < 1 || taps > 1024 || B < 0 || C < 0 || H < 0 || W < 0 || !sizes_ok(B, C, H, W) ||
+        (__int128)B * (C > taps ? C : taps) * (H + taps) * (W + taps) >= ((__int128)1 << 46))
+        return fail(SSTEM_ERR_BAD_SHAPE, "%s: bad shape or filter length", what);
+    if (algo != SSTEM_SEPCONV_AUTO && algo != SSTEM_SEPCONV_DIRECT && algo != SSTEM_SEPCONV_MFMA)
+        return fail(SSTEM_ERR_UNSUPPORTED, "%s: unknown algorithm id", what);
+    if (B == 0 || C == 0) return SSTEM_OK;
+    if (!grad_input || ((H > 0 && W > 0) && (!grad_output || !vertical || !horizontal)))
+        return fail(SSTEM_ERR_NULL_POINTER, "%s: null tensor pointer", what);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (H == 0 || W == 0) {   // no source pixel: every grad_input element is an empty sum
+        const size_t bytes = (size_t)B * C * (H + taps - 1) * (W + taps - 1) * sizeof(float);
+        if (bytes == 0) return SSTEM_OK;
+        hipError_t e = hipMemsetAsync(grad_input, 0, bytes, s);
+        if (e != hipSuccess) return hip_fail("sepconv input gradient memset", e);
+        return SSTEM_OK;
+    }
+    const bool tiled_can = !bf16 && taps == SSTEM_SEPCONV_FILTER && sstem::gradinput_tiled_ok(B, C, H, W);
+    if (algo == SSTEM_SEPCONV_AUTO) algo = tiled_can ? SSTEM_SEPCONV_MFMA : SSTEM_SEPCONV_DIRECT;
+    hipError_t e;
+    if (algo == SSTEM_SEPCONV_MFMA) {
+        if (!tiled_can) return fail(SSTEM_ERR_UNSUPPORTED, "%s: shape outside the tiled kernel's grid or 32-bit offset range", what);
+        e = sstem::launch_gradinput_tiled(grad_output, vertical, horizontal, grad_input, B, C, H, W, s);
+    } else {
+        e = sstem::launch_gradinput_direct(grad_output, vertical, horizontal, grad_input, B, C, H, W, taps, bf16, s);
+    }
+    if (e != hipSuccess) return hip_fail("sepconv input gradient launch", e);
+    return SSTEM_OK;
+}
+
+int sstem_sepconv_backward_input_f32_algo(const float* grad_output, const float* vertical, const float* horizontal, float* grad_input,
+                                          int64_t B, int64_t C, int64_t H, int64_t W, void* stream, int algo)
+{
+    return backward_input("backward input", grad_output, vertical, horizontal, grad_input, B, C, H, W, SSTEM_SEPCONV_FILTER, false, stream, algo);
+}
+
+int sstem_sepconv_backward_input_f32(const float* grad_output, const float* vertical, const float* horizontal, float* grad_input,
+                                     int64_t B, int64_t C, int64_t H, int64_t W, void* stream)
+{
+    return sstem_sepconv_backward_input_f32_algo(grad_output, vertical, horizontal, grad_input, B, C, H, W, stream, SSTEM_SEPCONV_AUTO);
+}
+
+int sstem_sepconv_backward_input_taps_f32(const float* grad_output, const float* vertical, const float* horizontal, float* grad_input,
+                                          int64_t B, int64_t C, int64_t H, int64_t W, int taps, void* stream)
+{
+    if (taps == SSTEM_SEPCONV_FILTER) return sstem_sepconv_backward_input_f32(grad_output, vertical, horizontal, grad_input, B, C, H, W, stream);
+    return backward_input("backward input (any filter length)", grad_output, vertical, horizontal, grad_input, B, C, H, W, taps, false, stream,
+                          SSTEM_SEPCONV_DIRECT);
+}
+
+int sstem_sepconv_backward_input_bf16coef(const float* grad_output, const uint16_t* vertical, const uint16_t* horizontal,
+                                          float* grad_input, int64_t B, int64_t C, int64_t H, int64_t W, void* stream)
+{
+    return backward_input("backward input (bf16 coefficients)", grad_output, reinterpret_cast<const float*>(vertical),
+                          reinterpret_cast<const float*>(horizontal), grad_input, B, C, H, W, SSTEM_SEPCONV_FILTER, true, stream,
+                          SSTEM_SEPCONV_DIRECT);
+}
+
 int64_t sstem_l1_workspace_floats(void) { return 1024 + 1; }
 
 int sstem_l1_mean_forward_grad_f32(const float* pred, const float* target, int64_t n, float* loss, float* grad, float* workspace,

@@ -21,6 +21,7 @@ import torch
 __all__ = [
     "SeparableConvolution_cuda_forward",
     "SeparableConvolution_cuda_backward",
+    "SeparableConvolution_cuda_backward_input",
     "library_path",
     "load_library",
 ]
@@ -126,4 +127,32 @@ def SeparableConvolution_cuda_backward(gradLoss, input, vertical, horizontal,
                 B, C, H, W, stream, _forced_algo)
     if rc != 0:
         _raise_status(lib, rc, "sstem_sepconv_backward_bf16coef" if bf16 else "sstem_sepconv_backward_f32")
+    return 1
+
+
+def SeparableConvolution_cuda_backward_input(gradLoss, vertical, horizontal, gradInput):
+    """gradInput[B,C,H+50,W+50] = the input gradient of the op -- this package's addition: the reference's backward never writes its
+    gradInput (kernel.cu:152-206).  Every element is written; ``set_algorithm`` is honoured (fp32 coefficients)."""
+    lib = load_library()
+    ts = [_dev_tensor(gradLoss, "gradLoss"), _dev_tensor(vertical, "vertical", coef=True),
+          _dev_tensor(horizontal, "horizontal", coef=True), _dev_tensor(gradInput, "gradInput")]
+    if vertical.dtype != horizontal.dtype:
+        raise TypeError("vertical and horizontal must have one dtype (%s vs %s)" % (vertical.dtype, horizontal.dtype))
+    bf16 = vertical.dtype == torch.bfloat16
+    dev = _same_device(ts)
+    B, C, H, W = gradLoss.shape
+    if tuple(gradInput.shape) != (B, C, H + 50, W + 50) or tuple(vertical.shape) != (B, 51, H, W) \
+            or tuple(horizontal.shape) != (B, 51, H, W):
+        raise RuntimeError("sepconv backward input: inconsistent shapes g=%s v=%s h=%s gradInput=%s" % (
+            tuple(gradLoss.shape), tuple(vertical.shape), tuple(horizontal.shape), tuple(gradInput.shape)))
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        if bf16:
+            rc = lib.sstem_sepconv_backward_input_bf16coef(gradLoss.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(),
+                                                           gradInput.data_ptr(), B, C, H, W, stream)
+        else:
+            rc = lib.sstem_sepconv_backward_input_f32_algo(gradLoss.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(),
+                                                           gradInput.data_ptr(), B, C, H, W, stream, _forced_algo)
+    if rc != 0:
+        _raise_status(lib, rc, "sstem_sepconv_backward_input_bf16coef" if bf16 else "sstem_sepconv_backward_input_f32")
     return 1

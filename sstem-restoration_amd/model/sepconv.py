@@ -9,6 +9,7 @@ the same shape and contiguity assertions (``:88-93``) and ``NotImplementedError`
 import torch
 
 import sstem_native
+from libs.sepconv import get_input_gradient                   # the package's input-gradient switch covers this op too
 from libs.sepconv.SeparableConvolution import SeparableConvolution
 
 
@@ -41,7 +42,16 @@ class _FunctionSepconvTaps(torch.autograd.Function):
                                                      gv.data_ptr(), gh.data_ptr(), B, C, H, W, vertical.shape[1],
                                                      torch.cuda.current_stream().cuda_stream)
         sstem_native.check(rc, "sstem_sepconv_backward_taps_f32")
-        return torch.zeros_like(input), gv, gh          # grad_input: zeros, as the compiled op of the reference leaves it (kernel.cu:152-206)
+        if not get_input_gradient():
+            return torch.zeros_like(input), gv, gh      # grad_input: zeros, as the compiled op of the reference leaves it (kernel.cu:152-206)
+        gi = None                                       # the switch is on: computed where asked for, None otherwise
+        if ctx.needs_input_grad[0]:
+            gi = torch.empty_like(input)
+            with torch.cuda.device(input.device):
+                rc = lib.sstem_sepconv_backward_input_taps_f32(grad_output.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), gi.data_ptr(),
+                                                               B, C, H, W, vertical.shape[1], torch.cuda.current_stream().cuda_stream)
+            sstem_native.check(rc, "sstem_sepconv_backward_input_taps_f32")
+        return gi, gv, gh
 
 
 def FunctionSepconv(tenInput, tenVertical, tenHorizontal):

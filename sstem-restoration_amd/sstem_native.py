@@ -40,6 +40,11 @@ C_ABI = {
     "sstem_sepconv_forward_bytes_bf16coef": (_i64, [_i64] * 4),
     "sstem_sepconv_backward_bytes_bf16coef": (_i64, [_i64] * 4),
     "sstem_sepconv_interp_apply_bytes_bf16coef": (_i64, [_i64] * 3 + [_int]),
+    "sstem_sepconv_backward_input_f32": (_int, [_p] * 4 + [_i64] * 4 + [_p]),
+    "sstem_sepconv_backward_input_f32_algo": (_int, [_p] * 4 + [_i64] * 4 + [_p, _int]),
+    "sstem_sepconv_backward_input_taps_f32": (_int, [_p] * 4 + [_i64] * 4 + [_int, _p]),
+    "sstem_sepconv_backward_input_bf16coef": (_int, [_p] * 4 + [_i64] * 4 + [_p]),
+    "sstem_sepconv_backward_input_bytes": (_i64, [_i64] * 4),
     "sstem_version": (_int, []),
     "sstem_status_string": (ctypes.c_char_p, [_int]),
     "sstem_last_error": (ctypes.c_char_p, []),

@@ -29,9 +29,60 @@ ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--algo", type=int, default=0)
 ap.add_argument("--what", default="fwd,bwd,fused")
 ap.add_argument("--gray", action="store_true", help="grayscale frames replicated to 3 identical channels")
+ap.add_argument("--grad-input", action="store_true",
+                help="time sstem_sepconv_backward_input_f32_algo (direct and tiled) beside the existing backward call at the same "
+                     "shape, alternating, at C2 (8 x 3 x 1024^2), C = 1 and 64 x 3 x 256^2; --rounds repeats the alternation")
+ap.add_argument("--rounds", type=int, default=3)
 a = ap.parse_args()
 cunnex.set_algorithm(a.algo)
 lib = cunnex.load_library()
+
+
+def _events(fn, n):
+    fn()
+    torch.cuda.synchronize()
+    e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def grad_input_arm():
+    stream = torch.cuda.current_stream().cuda_stream
+    for B, C, S in ((8, 3, 1024), (8, 1, 1024), (64, 3, 256)):
+        torch.manual_seed(555)
+        inp = torch.rand(B, C, S + 50, S + 50, device="cuda")
+        ver = torch.softmax(torch.randn(B, 51, S, S, device="cuda"), 1)
+        hor = torch.softmax(torch.randn(B, 51, S, S, device="cuda"), 1)
+        g = torch.randn(B, C, S, S, device="cuda")
+        gi, gv, gh = torch.empty_like(inp), torch.empty_like(ver), torch.empty_like(hor)
+
+        def run_gi(algo):
+            rc = lib.sstem_sepconv_backward_input_f32_algo(g.data_ptr(), ver.data_ptr(), hor.data_ptr(), gi.data_ptr(), B, C, S, S, stream, algo)
+            assert rc == 0, lib.sstem_last_error()
+
+        arms = [("backward (gV + gH)", lambda: cunnex.SeparableConvolution_cuda_backward(g, inp, ver, hor, None, gv, gh), a.iters,
+                 lib.sstem_sepconv_backward_bytes(B, C, S, S)),
+                ("grad_input tiled", lambda: run_gi(cunnex.ALGO_MFMA), a.iters, lib.sstem_sepconv_backward_input_bytes(B, C, S, S)),
+                ("grad_input direct", lambda: run_gi(cunnex.ALGO_DIRECT), max(1, a.iters // 5), lib.sstem_sepconv_backward_input_bytes(B, C, S, S))]
+        best = {}
+        for _ in range(a.rounds):                              # alternating: every arm sees the same clocks and neighbours
+            for name, fn, n, by in arms:
+                ms = _events(fn, n)
+                best.setdefault(name, []).append(ms)
+        for name, fn, n, by in arms:
+            ms = sorted(best[name])[len(best[name]) // 2]
+            print("%dx%dx%dx%d  %-20s median %.4f ms  (rounds: %s)  %.0f GB/s = %.1f%% of 8 TB/s on the byte model" % (
+                B, C, S, S, name, ms, " ".join("%.3f" % m for m in best[name]), by / ms / 1e6, by / ms / 1e6 / 80))
+        del inp, ver, hor, g, gi, gv, gh
+        torch.cuda.empty_cache()
+
+
+if a.grad_input:
+    grad_input_arm()
+    sys.exit(0)
 B, S = a.batch, a.size
 torch.manual_seed(555)
 inp = torch.rand(B, 1 if a.gray else 3, S + 50, S + 50, device="cuda").expand(B, 3, S + 50, S + 50).contiguous()
