@@ -22,15 +22,21 @@ namespace {
 
 thread_local char g_last_error[512] = "";
 
-int fail(int status, const char* fmt, const char* a = "", const char* b = "")
+int fail(int status, const char* fmt, const char* a = "", const char* b = "", const char* c = "")
 {
-    snprintf(g_last_error, sizeof(g_last_error), fmt, a, b);
+    snprintf(g_last_error, sizeof(g_last_error), fmt, a, b, c);
     return status;
 }
 
-int hip_fail(const char* where, hipError_t e)
+int hip_fail(const char* where, hipError_t e, const char* step = "")
 {
-    return fail(SSTEM_ERR_HIP, "%s: %s", where, hipGetErrorString(e));
+    return fail(SSTEM_ERR_HIP, "%s%s: %s", where, step, hipGetErrorString(e));
+}
+
+// the end of every entry: the status of its last HIP call.  The shared bodies below pass their caller's prefix and " launch".
+int launched(const char* where, hipError_t e, const char* step = "")
+{
+    return e == hipSuccess ? SSTEM_OK : hip_fail(where, e, step);
 }
 
 // all element counts of a call must be addressable in int64 (the reference used 32-bit int,
@@ -45,11 +51,157 @@ bool sizes_ok(int64_t B, int64_t C, int64_t H, int64_t W)
     return big < ((__int128)1 << 46);
 }
 
-}  // namespace
+// the entries that take a filter length: 1..1024 taps, and the padded tensors addressable as in sizes_ok
+bool taps_sizes_ok(int64_t B, int64_t C, int64_t H, int64_t W, int taps)
+{
+    return taps >= 1 && taps <= 1024 && B >= 0 && C >= 0 && H >= 0 && W >= 0 &&
+           (__int128)B * (C > taps ? C : taps) * (H + taps) * (W + taps) < ((__int128)1 << 46);
+}
+
+// ---- fused interpolation apply: the `_supported` queries and the entries evaluate the same predicates, the five entries share a body --
+enum ApplyKind { APPLY_RGB, APPLY_GRAY, APPLY_GRAY_BLOCKED, APPLY_GRAY_BF16COEF };
+
+// one image's coefficients sit behind a 32-bit buffer resource (the rgb kernel has no such bound)
+bool apply_range_ok(ApplyKind kind, int64_t H, int64_t W)
+{
+    switch (kind) {
+        case APPLY_GRAY: return sstem::interp_fused_gray_ok(H, W);
+        case APPLY_GRAY_BLOCKED: return sstem::interp_fused_gray_blocked_ok(H, W);
+        case APPLY_GRAY_BF16COEF: return sstem::interp_fused_gray_bf16coef_ok(H, W);
+        default: return true;
+    }
+}
+
+int apply_supported(ApplyKind kind, int64_t B, int64_t H, int64_t W)
+{
+    return (sizes_ok(B, 3, H, W) && B > 0 && H > 0 && W > 0 && sstem::mfma_grid_ok(B, H, W) && apply_range_ok(kind, H, W)) ? 1 : 0;
+}
+
+// grid_note, range_note: the entry's own words for the two range refusals; launch(): its launcher on its tensors
+template <class Launch>
+int interp_apply(const char* what, ApplyKind kind, bool any_null, int64_t B, int64_t H, int64_t W, const char* grid_note,
+                 const char* range_note, Launch launch)
+{
+    if (!sizes_ok(B, 3, H, W)) return fail(SSTEM_ERR_BAD_SHAPE, "%s: negative or oversized shape", what);
+    if (B == 0 || H == 0 || W == 0) return SSTEM_OK;
+    if (any_null) return fail(SSTEM_ERR_NULL_POINTER, "%s: null tensor pointer", what);
+    if (!sstem::mfma_grid_ok(B, H, W)) return fail(SSTEM_ERR_UNSUPPORTED, "%s: %s", what, grid_note);
+    if (!apply_range_ok(kind, H, W)) return fail(SSTEM_ERR_UNSUPPORTED, "%s: %s", what, range_note);
+    return launched(what, launch(), " launch");
+}
+
+// ---- dense convolutions: the small rules, written once -------------------------------------------------------------------------
+bool conv_sizes_ok(int64_t N, int64_t Cin, int64_t H, int64_t W, int64_t Cout)
+{
+    if (N < 0 || Cin < 0 || H < 0 || W < 0 || Cout < 0) return false;
+    const int64_t lim = (int64_t)1 << 30;
+    if (N > lim || Cin > lim || Cout > lim || H > lim || W > lim) return false;
+    if (H * W >= ((int64_t)1 << 31)) return false;               // in-plane offsets are 32-bit
+    if ((__int128)N * (Cin > Cout ? Cin : Cout) * H * W >= ((__int128)1 << 46)) return false;
+    return true;
+}
+
+// ... and none of the five sizes is zero: the entries and queries with no empty-shape case
+bool conv_sizes_positive(int64_t N, int64_t Cin, int64_t H, int64_t W, int64_t Cout)
+{
+    return conv_sizes_ok(N, Cin, H, W, Cout) && N > 0 && Cin > 0 && H > 0 && W > 0 && Cout > 0;
+}
+
+bool channels_ok(int64_t Cin, int64_t Cout) { return Cin > 0 && Cout > 0 && Cin <= (1 << 20) && Cout <= (1 << 20); }
+
+// 0, or the refusal of an activation id / a weight-flags word outside the values of include/sstem_conv.h
+bool act_ok(int act) { return act >= 0 && act <= 2; }
+int check_act(const char* what, int act) { return act_ok(act) ? 0 : fail(SSTEM_ERR_UNSUPPORTED, "%s: unknown activation id", what); }
+int check_weight_flags(const char* what, int flags)
+{
+    return flags >= 0 && flags <= 3 ? 0 : fail(SSTEM_ERR_UNSUPPORTED, "%s: unknown weight flags", what);
+}
 
 // weight-gradient launches: bit 0 = add into the gradient buffers, bit 1 (only with bit 0) = defer the slab reduce to
 // sstem_wgrad_deferred_flush (include/sstem_conv.h)
-static inline int wgrad_flags(int accumulate) { return accumulate == 3 ? 3 : (accumulate ? 1 : 0); }
+int wgrad_flags(int accumulate) { return accumulate == 3 ? 3 : (accumulate ? 1 : 0); }
+
+// An algorithm id of include/sstem_conv.h as the kernel family behind it; the split ids carry their pieces per operand and whether
+// those are fp16.  SSTEM_CONV_AUTO and unknown ids are FAMILY_NONE: each entry says what it makes of them.
+enum ConvFamily { FAMILY_NONE, FAMILY_DIRECT, FAMILY_FP32, FAMILY_BF16, FAMILY_SPLIT };
+struct ConvAlgo {
+    ConvFamily family;
+    int pieces, f16;
+    bool split_bf16() const { return family == FAMILY_SPLIT && !f16; }      // the two ids that every split entry takes
+};
+ConvAlgo conv_algo(int algo)
+{
+    switch (algo) {
+        case SSTEM_CONV_DIRECT: return {FAMILY_DIRECT, 0, 0};
+        case SSTEM_CONV_MFMA: return {FAMILY_FP32, 0, 0};
+        case SSTEM_CONV_MFMA_BF16: return {FAMILY_BF16, 0, 0};
+        case SSTEM_CONV_MFMA_BF16X3: return {FAMILY_SPLIT, 2, 0};
+        case SSTEM_CONV_MFMA_BF16X6: return {FAMILY_SPLIT, 3, 0};
+        case SSTEM_CONV_MFMA_F16X3: return {FAMILY_SPLIT, 2, 1};
+        default: return {FAMILY_NONE, 0, 0};
+    }
+}
+
+// the end of the three forward entries of the split kernels, after their own argument checks: range, workspace, launch
+// (ex.f16: the pieces are fp16).  range_note: what the entry's range refusal adds
+int split_forward(const char* what, const char* range_note, const float* input, const float* weight, const float* bias, const float* scale,
+                  const float* shift, float* output, float* workspace, int64_t workspace_floats, int64_t N, int64_t Cin, int64_t H,
+                  int64_t W, int64_t Cout, int weight_flags, int act, float slope, int pieces, const sstem::ConvExtra& ex, void* stream)
+{
+    if (!sstem::conv3x3_split_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout) ||
+        (ex.f16 && !sstem::conv3x3_split_f16_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout)))
+        return fail(SSTEM_ERR_UNSUPPORTED, "%s: outside the split kernel's range%s", what, range_note);
+    if (!workspace || workspace_floats < sstem::conv3x3_split_packed_floats((int)Cin, (int)Cout, pieces, ex.f16))
+        return fail(SSTEM_ERR_BAD_SHAPE, "%s: workspace too small (see sstem_conv3x3_forward_workspace_floats_algo)", what);
+    return launched(what, sstem::launch_conv3x3_split_mfma(input, weight, bias, scale, shift, output, workspace, workspace_floats, (int)N,
+                                                           (int)Cin, (int)H, (int)W, (int)Cout, act, slope, weight_flags, pieces,
+                                                           static_cast<hipStream_t>(stream), ex), " launch");
+}
+
+// the bf16-operand forward with fp32 or bf16 tensors at either end; the plain entry is the masked one without masks
+int forward_bf16io(const char* what, const void* input, int input_bf16, const uint8_t* input_mask, const float* weight, const float* bias,
+                   const float* scale, const float* shift, void* output, int output_bf16, uint8_t* output_mask, float* workspace,
+                   int64_t workspace_floats, int64_t N, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int weight_flags, int act,
+                   float slope, void* stream)
+{
+    if (!conv_sizes_ok(N, Cin, H, W, Cout)) return fail(SSTEM_ERR_BAD_SHAPE, "%s: bad shape", what);
+    if (int rc = check_act(what, act)) return rc;
+    if (int rc = check_weight_flags(what, weight_flags)) return rc;
+    if (N == 0 || Cout == 0 || H == 0 || W == 0) return SSTEM_OK;
+    if (!input || !weight || !output) return fail(SSTEM_ERR_NULL_POINTER, "%s: null tensor pointer", what);
+    if (input_bf16 && input_mask) return fail(SSTEM_ERR_UNSUPPORTED, "%s: input_mask needs an fp32 input tensor", what);
+    if ((input_mask || output_mask) && (reinterpret_cast<uintptr_t>(input) & 15) != 0)
+        return fail(SSTEM_ERR_UNSUPPORTED, "%s: the masks need a 16-byte aligned input", what);
+    if (Cin == 0 || !sstem::conv3x3_bf16_io_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout, output_bf16))
+        return fail(SSTEM_ERR_UNSUPPORTED, "%s: needs W %% 4 == 0, a channel plane below 2 GiB and, for a bf16 output, an unsplit launch "
+                                           "(sstem_conv3x3_bf16io_supported)", what);
+    if (!workspace || workspace_floats < sstem::conv3x3_bf16_packed_floats((int)Cin, (int)Cout))
+        return fail(SSTEM_ERR_BAD_SHAPE, "%s: workspace too small (see sstem_conv3x3_forward_workspace_floats_algo)", what);
+    return launched(what, sstem::launch_conv3x3_bf16_mfma_io(input, input_bf16 ? 1 : 0, weight, bias, scale, shift, output, output_bf16 ? 1 : 0,
+                                                             workspace, workspace_floats, (int)N, (int)Cin, (int)H, (int)W, (int)Cout, act,
+                                                             slope, weight_flags, static_cast<hipStream_t>(stream), input_mask, output_mask),
+                    " launch");
+}
+
+// the two weight-gradient entries of the split kernels.  pieces == 0: the caller's algorithm id is no split-bf16 id
+int backward_weight_split(const char* what, int pieces, bool any_null, const float* input, const float* input_amax, const float* grad_output,
+                          const float* grad_amax, const uint8_t* grad_mask, float* grad_weight, float* grad_bias, float* workspace,
+                          int64_t workspace_floats, int64_t N, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int accumulate, void* stream)
+{
+    if (!conv_sizes_positive(N, Cin, H, W, Cout)) return fail(SSTEM_ERR_BAD_SHAPE, "%s: bad shape", what);
+    if (!pieces) return fail(SSTEM_ERR_UNSUPPORTED, "%s: a split-bf16 id is needed (SSTEM_CONV_MFMA_BF16X6 / _BF16X3)", what);
+    if (any_null) return fail(SSTEM_ERR_NULL_POINTER, "%s: null tensor pointer", what);
+    if (Cin * Cout >= ((int64_t)1 << 31)) return fail(SSTEM_ERR_BAD_SHAPE, "%s: Cin*Cout too large", what);
+    if (!sstem::conv3x3_wgrad_split_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout))
+        return fail(SSTEM_ERR_UNSUPPORTED, "%s: outside the split kernel's range", what);
+    if (!workspace || workspace_floats < sstem::conv3x3_wgrad_split_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout))
+        return fail(SSTEM_ERR_BAD_SHAPE, "%s: workspace too small (see sstem_conv3x3_wgrad_workspace_floats_algo)", what);
+    return launched(what, sstem::launch_conv3x3_wgrad_split_mfma(input, grad_output, grad_weight, grad_bias, workspace, (int)N, (int)Cin,
+                                                                 (int)H, (int)W, (int)Cout, pieces, static_cast<hipStream_t>(stream),
+                                                                 wgrad_flags(accumulate), grad_mask, input_amax, grad_amax), " launch");
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -58,8 +210,7 @@ void sstem_wgrad_deferred_drop(void) { sstem::wgrad_deferred_drop(); }
 int sstem_wgrad_deferred_flush(void* stream)
 {
     hipError_t e = sstem::wgrad_deferred_flush(static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("grouped weight-gradient reduce launch", e);
-    return SSTEM_OK;
+    return launched("grouped weight-gradient reduce launch", e);
 }
 
 int sstem_version(void) { return 100; }  // 0.1.0
@@ -111,8 +262,7 @@ int sstem_sepconv_forward_f32_algo(const float* input, const float* vertical,
     } else {
         return fail(SSTEM_ERR_UNSUPPORTED, "forward: unknown algorithm id");
     }
-    if (e != hipSuccess) return hip_fail("sepconv forward launch", e);
-    return SSTEM_OK;
+    return launched("sepconv forward launch", e);
 }
 
 int sstem_sepconv_forward_f32(const float* input, const float* vertical,
@@ -128,15 +278,21 @@ int sstem_sepconv_interp_apply_f32(const float* i1, const float* i2,
                                    const float* k2v, const float* k2h, float* output,
                                    int64_t B, int64_t H, int64_t W, void* stream)
 {
-    if (!sizes_ok(B, 3, H, W)) return fail(SSTEM_ERR_BAD_SHAPE, "interp apply: negative or oversized shape");
-    if (B == 0 || H == 0 || W == 0) return SSTEM_OK;
-    if (!i1 || !i2 || !k1v || !k1h || !k2v || !k2h || !output)
-        return fail(SSTEM_ERR_NULL_POINTER, "interp apply: null tensor pointer");
-    if (!sstem::mfma_grid_ok(B, H, W)) return fail(SSTEM_ERR_UNSUPPORTED, "interp apply: grid too large");
-    hipError_t e = sstem::launch_interp_fused(i1, i2, k1v, k1h, k2v, k2h, output, B, H, W,
-                                              static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("interp apply launch", e);
-    return SSTEM_OK;
+    return interp_apply("interp apply", APPLY_RGB, !i1 || !i2 || !k1v || !k1h || !k2v || !k2h || !output, B, H, W, "grid too large", "", [&] {
+        return sstem::launch_interp_fused(i1, i2, k1v, k1h, k2v, k2h, output, B, H, W, static_cast<hipStream_t>(stream));
+    });
+}
+
+// the three fp32 gray entries: the NCHW or the blocked kernel, with or without the uint8 copy of the output
+static int interp_apply_gray(const char* what, ApplyKind kind, const char* range_note, const float* g1, const float* g2, const float* k1v,
+                             const float* k1h, const float* k2v, const float* k2h, float* output, uint8_t* output_u8, bool need_u8,
+                             int64_t B, int64_t H, int64_t W, void* stream)
+{
+    const bool any_null = !g1 || !g2 || !k1v || !k1h || !k2v || !k2h || !output || (need_u8 && !output_u8);
+    return interp_apply(what, kind, any_null, B, H, W, "grid too large", range_note, [&] {
+        return (kind == APPLY_GRAY_BLOCKED ? sstem::launch_interp_fused_gray_blocked : sstem::launch_interp_fused_gray)(
+            g1, g2, k1v, k1h, k2v, k2h, output, B, H, W, static_cast<hipStream_t>(stream), output_u8);
+    });
 }
 
 int sstem_sepconv_interp_apply_gray_f32(const float* g1, const float* g2,
@@ -144,24 +300,12 @@ int sstem_sepconv_interp_apply_gray_f32(const float* g1, const float* g2,
                                         const float* k2v, const float* k2h, float* output,
                                         int64_t B, int64_t H, int64_t W, void* stream)
 {
-    if (!sizes_ok(B, 3, H, W)) return fail(SSTEM_ERR_BAD_SHAPE, "gray interp apply: negative or oversized shape");
-    if (B == 0 || H == 0 || W == 0) return SSTEM_OK;
-    if (!g1 || !g2 || !k1v || !k1h || !k2v || !k2h || !output)
-        return fail(SSTEM_ERR_NULL_POINTER, "gray interp apply: null tensor pointer");
-    if (!sstem::mfma_grid_ok(B, H, W)) return fail(SSTEM_ERR_UNSUPPORTED, "gray interp apply: grid too large");
-    if (!sstem::interp_fused_gray_ok(H, W))
-        return fail(SSTEM_ERR_UNSUPPORTED, "gray interp apply: 51*H*W*4 bytes per image must stay below 4 GiB "
-                                           "(use sstem_sepconv_interp_apply_f32 on the replicated frames)");
-    hipError_t e = sstem::launch_interp_fused_gray(g1, g2, k1v, k1h, k2v, k2h, output, B, H, W,
-                                                   static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("gray interp apply launch", e);
-    return SSTEM_OK;
+    return interp_apply_gray("gray interp apply", APPLY_GRAY, "51*H*W*4 bytes per image must stay below 4 GiB "
+                             "(use sstem_sepconv_interp_apply_f32 on the replicated frames)",
+                             g1, g2, k1v, k1h, k2v, k2h, output, nullptr, false, B, H, W, stream);
 }
 
-int sstem_sepconv_interp_apply_gray_supported(int64_t B, int64_t H, int64_t W)
-{
-    return (sizes_ok(B, 3, H, W) && B > 0 && H > 0 && W > 0 && sstem::mfma_grid_ok(B, H, W) && sstem::interp_fused_gray_ok(H, W)) ? 1 : 0;
-}
+int sstem_sepconv_interp_apply_gray_supported(int64_t B, int64_t H, int64_t W) { return apply_supported(APPLY_GRAY, B, H, W); }
 
 int64_t sstem_sepconv_coef_blocked_floats(int64_t B, int64_t H, int64_t W)
 {
@@ -175,50 +319,27 @@ int sstem_sepconv_coef_to_blocked_f32(const float* coef, float* blocked, int64_t
     if (B == 0 || H == 0 || W == 0) return SSTEM_OK;
     if (!coef || !blocked) return fail(SSTEM_ERR_NULL_POINTER, "coef to blocked: null tensor pointer");
     hipError_t e = sstem::launch_coef_to_blocked(coef, blocked, B, H, W, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("coef to blocked launch", e);
-    return SSTEM_OK;
+    return launched("coef to blocked launch", e);
 }
 
-int sstem_sepconv_interp_apply_gray_blocked_supported(int64_t B, int64_t H, int64_t W)
-{
-    return (sizes_ok(B, 3, H, W) && B > 0 && H > 0 && W > 0 && sstem::mfma_grid_ok(B, H, W) &&
-            sstem::interp_fused_gray_blocked_ok(H, W)) ? 1 : 0;
-}
+int sstem_sepconv_interp_apply_gray_blocked_supported(int64_t B, int64_t H, int64_t W) { return apply_supported(APPLY_GRAY_BLOCKED, B, H, W); }
 
 int sstem_sepconv_interp_apply_gray_blocked_f32(const float* g1, const float* g2,
                                                 const float* k1v, const float* k1h,
                                                 const float* k2v, const float* k2h, float* output,
                                                 int64_t B, int64_t H, int64_t W, void* stream)
 {
-    if (!sizes_ok(B, 3, H, W)) return fail(SSTEM_ERR_BAD_SHAPE, "blocked gray interp apply: negative or oversized shape");
-    if (B == 0 || H == 0 || W == 0) return SSTEM_OK;
-    if (!g1 || !g2 || !k1v || !k1h || !k2v || !k2h || !output)
-        return fail(SSTEM_ERR_NULL_POINTER, "blocked gray interp apply: null tensor pointer");
-    if (!sstem::mfma_grid_ok(B, H, W)) return fail(SSTEM_ERR_UNSUPPORTED, "blocked gray interp apply: grid too large");
-    if (!sstem::interp_fused_gray_blocked_ok(H, W))
-        return fail(SSTEM_ERR_UNSUPPORTED, "blocked gray interp apply: one image's blocked coefficients must stay below 4 GiB");
-    hipError_t e = sstem::launch_interp_fused_gray_blocked(g1, g2, k1v, k1h, k2v, k2h, output, B, H, W,
-                                                           static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("blocked gray interp apply launch", e);
-    return SSTEM_OK;
+    return interp_apply_gray("blocked gray interp apply", APPLY_GRAY_BLOCKED, "one image's blocked coefficients must stay below 4 GiB",
+                             g1, g2, k1v, k1h, k2v, k2h, output, nullptr, false, B, H, W, stream);
 }
 
 int sstem_sepconv_interp_apply_gray_u8_f32(const float* g1, const float* g2, const float* k1v, const float* k1h,
                                            const float* k2v, const float* k2h, float* output, uint8_t* output_u8,
                                            int64_t B, int64_t H, int64_t W, int blocked_coefficients, void* stream)
 {
-    if (!sizes_ok(B, 3, H, W)) return fail(SSTEM_ERR_BAD_SHAPE, "gray interp apply (uint8 store): negative or oversized shape");
-    if (B == 0 || H == 0 || W == 0) return SSTEM_OK;
-    if (!g1 || !g2 || !k1v || !k1h || !k2v || !k2h || !output || !output_u8)
-        return fail(SSTEM_ERR_NULL_POINTER, "gray interp apply (uint8 store): null tensor pointer");
-    if (!sstem::mfma_grid_ok(B, H, W)) return fail(SSTEM_ERR_UNSUPPORTED, "gray interp apply (uint8 store): grid too large");
-    if (blocked_coefficients ? !sstem::interp_fused_gray_blocked_ok(H, W) : !sstem::interp_fused_gray_ok(H, W))
-        return fail(SSTEM_ERR_UNSUPPORTED, "gray interp apply (uint8 store): one image's coefficients must stay below 4 GiB");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = blocked_coefficients ? sstem::launch_interp_fused_gray_blocked(g1, g2, k1v, k1h, k2v, k2h, output, B, H, W, s, output_u8)
-                                        : sstem::launch_interp_fused_gray(g1, g2, k1v, k1h, k2v, k2h, output, B, H, W, s, output_u8);
-    if (e != hipSuccess) return hip_fail("gray interp apply (uint8 store) launch", e);
-    return SSTEM_OK;
+    return interp_apply_gray("gray interp apply (uint8 store)", blocked_coefficients ? APPLY_GRAY_BLOCKED : APPLY_GRAY,
+                             "one image's coefficients must stay below 4 GiB", g1, g2, k1v, k1h, k2v, k2h, output, output_u8, true, B, H, W,
+                             stream);
 }
 
 int64_t sstem_sepconv_interp_apply_bytes(int64_t B, int64_t H, int64_t W, int frame_planes)
@@ -246,8 +367,7 @@ int sstem_sepconv_backward_f32_algo(const float* grad_output, const float* input
         const size_t bytes = (size_t)B * 51 * H * W * sizeof(float);
         hipError_t e = hipMemsetAsync(grad_vertical, 0, bytes, s);
         if (e == hipSuccess) e = hipMemsetAsync(grad_horizontal, 0, bytes, s);
-        if (e != hipSuccess) return hip_fail("sepconv backward memset", e);
-        return SSTEM_OK;
+        return launched("sepconv backward memset", e);
     }
     hipError_t e;
     if (algo == SSTEM_SEPCONV_AUTO)
@@ -262,8 +382,7 @@ int sstem_sepconv_backward_f32_algo(const float* grad_output, const float* input
     } else {
         return fail(SSTEM_ERR_UNSUPPORTED, "backward: unknown algorithm id");
     }
-    if (e != hipSuccess) return hip_fail("sepconv backward launch", e);
-    return SSTEM_OK;
+    return launched("sepconv backward launch", e);
 }
 
 int sstem_sepconv_backward_f32(const float* grad_output, const float* input,
@@ -279,18 +398,8 @@ int sstem_sepconv_backward_f32(const float* grad_output, const float* input,
 // ---- dense convolution blocks (include/sstem_conv.h) -------------------------------------------
 int64_t sstem_conv3x3_workspace_floats(int64_t Cin, int64_t Cout)
 {
-    if (Cin <= 0 || Cout <= 0 || Cin > (1 << 20) || Cout > (1 << 20)) return 0;
+    if (!channels_ok(Cin, Cout)) return 0;
     return sstem::conv3x3_workspace_floats((int)Cin, (int)Cout);
-}
-
-static bool conv_sizes_ok(int64_t N, int64_t Cin, int64_t H, int64_t W, int64_t Cout)
-{
-    if (N < 0 || Cin < 0 || H < 0 || W < 0 || Cout < 0) return false;
-    const int64_t lim = (int64_t)1 << 30;
-    if (N > lim || Cin > lim || Cout > lim || H > lim || W > lim) return false;
-    if (H * W >= ((int64_t)1 << 31)) return false;               // in-plane offsets are 32-bit
-    if ((__int128)N * (Cin > Cout ? Cin : Cout) * H * W >= ((__int128)1 << 46)) return false;
-    return true;
 }
 
 int64_t sstem_conv3x3_forward_workspace_floats(int64_t N, int64_t Cin, int64_t H, int64_t W, int64_t Cout)
@@ -299,52 +408,51 @@ int64_t sstem_conv3x3_forward_workspace_floats(int64_t N, int64_t Cin, int64_t H
     return sstem::conv3x3_forward_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout);
 }
 
-// pieces per operand of the split ids (0: not a split id)
-static inline int split_pieces_of(int algo) { return algo == SSTEM_CONV_MFMA_BF16X3 ? 2 : algo == SSTEM_CONV_MFMA_BF16X6 ? 3 : 0; }
-// ... and of the scaled-forward entry's ids (the fp16 id has two)
-static inline int scaled_pieces_of(int algo) { return algo == SSTEM_CONV_MFMA_F16X3 ? 2 : split_pieces_of(algo); }
-
 int64_t sstem_conv3x3_packed_floats(int64_t Cin, int64_t Cout, int algo)
 {
-    if (Cin <= 0 || Cout <= 0 || Cin > (1 << 20) || Cout > (1 << 20)) return 0;
-    if (algo == SSTEM_CONV_MFMA_BF16) return sstem::conv3x3_bf16_packed_floats((int)Cin, (int)Cout);
-    if (split_pieces_of(algo)) return sstem::conv3x3_split_packed_floats((int)Cin, (int)Cout, split_pieces_of(algo));
-    if (algo == SSTEM_CONV_MFMA_F16X3) return sstem::conv3x3_split_packed_floats((int)Cin, (int)Cout, 2, 1);
-    if (algo == SSTEM_CONV_MFMA) return sstem::conv3x3_workspace_floats((int)Cin, (int)Cout);
-    return 0;
+    if (!channels_ok(Cin, Cout)) return 0;
+    const ConvAlgo a = conv_algo(algo);
+    switch (a.family) {
+        case FAMILY_BF16: return sstem::conv3x3_bf16_packed_floats((int)Cin, (int)Cout);
+        case FAMILY_SPLIT: return sstem::conv3x3_split_packed_floats((int)Cin, (int)Cout, a.pieces, a.f16);
+        case FAMILY_FP32: return sstem::conv3x3_workspace_floats((int)Cin, (int)Cout);
+        default: return 0;
+    }
 }
 
 int sstem_conv3x3_pack_weights_f32(const float* weight, int64_t Cin, int64_t Cout, int algo, float* packed_forward,
                                    float* packed_transposed, void* stream)
 {
-    if (Cin <= 0 || Cout <= 0 || Cin > (1 << 20) || Cout > (1 << 20)) return fail(SSTEM_ERR_BAD_SHAPE, "pack_weights: bad shape");
+    if (!channels_ok(Cin, Cout)) return fail(SSTEM_ERR_BAD_SHAPE, "pack_weights: bad shape");
     if (!weight) return fail(SSTEM_ERR_NULL_POINTER, "pack_weights: null weight");
     if (!packed_forward && !packed_transposed) return SSTEM_OK;
+    const ConvAlgo a = conv_algo(algo);
+    hipStream_t s = static_cast<hipStream_t>(stream);
     hipError_t e;
-    if (algo == SSTEM_CONV_MFMA_BF16)
-        e = sstem::launch_pack_weights_3x3_bf16_both(weight, packed_forward, packed_transposed, (int)Cin, (int)Cout, static_cast<hipStream_t>(stream));
-    else if (split_pieces_of(algo))
-        e = sstem::launch_pack_weights_3x3_split_both(weight, packed_forward, packed_transposed, (int)Cin, (int)Cout, split_pieces_of(algo),
-                                                      static_cast<hipStream_t>(stream));
-    else if (algo == SSTEM_CONV_MFMA_F16X3)
-        e = sstem::launch_pack_weights_3x3_split_f16_both(weight, packed_forward, packed_transposed, (int)Cin, (int)Cout,
-                                                          static_cast<hipStream_t>(stream));
-    else if (algo == SSTEM_CONV_MFMA)
-        e = sstem::launch_pack_weights_3x3_both(weight, packed_forward, packed_transposed, (int)Cin, (int)Cout, static_cast<hipStream_t>(stream));
-    else
-        return fail(SSTEM_ERR_UNSUPPORTED, "pack_weights: an explicit MFMA algorithm id is needed (SSTEM_CONV_MFMA or _MFMA_BF16)");
-    if (e != hipSuccess) return hip_fail("pack_weights launch", e);
-    return SSTEM_OK;
+    switch (a.family) {
+        case FAMILY_BF16: e = sstem::launch_pack_weights_3x3_bf16_both(weight, packed_forward, packed_transposed, (int)Cin, (int)Cout, s); break;
+        case FAMILY_SPLIT:
+            e = a.f16 ? sstem::launch_pack_weights_3x3_split_f16_both(weight, packed_forward, packed_transposed, (int)Cin, (int)Cout, s)
+                      : sstem::launch_pack_weights_3x3_split_both(weight, packed_forward, packed_transposed, (int)Cin, (int)Cout, a.pieces, s);
+            break;
+        case FAMILY_FP32: e = sstem::launch_pack_weights_3x3_both(weight, packed_forward, packed_transposed, (int)Cin, (int)Cout, s); break;
+        default: return fail(SSTEM_ERR_UNSUPPORTED, "pack_weights: an explicit MFMA algorithm id is needed (SSTEM_CONV_MFMA or _MFMA_BF16)");
+    }
+    return launched("pack_weights launch", e);
 }
 
 int64_t sstem_conv3x3_pack_group_entry(int64_t Cin, int64_t Cout, int algo, int64_t* entry16)
 {
-    if (!entry16 || Cin <= 0 || Cout <= 0 || Cin > (1 << 20) || Cout > (1 << 20)) return 0;
-    if (algo == SSTEM_CONV_MFMA_BF16) return sstem::pack_group_entry_bf16((int)Cin, (int)Cout, entry16);
-    if (split_pieces_of(algo)) return sstem::pack_group_entry_split((int)Cin, (int)Cout, split_pieces_of(algo), entry16);
-    if (algo == SSTEM_CONV_MFMA_F16X3) return sstem::pack_group_entry_split_f16((int)Cin, (int)Cout, entry16);
-    if (algo == SSTEM_CONV_MFMA) return sstem::pack_group_entry((int)Cin, (int)Cout, entry16);
-    return 0;
+    if (!entry16 || !channels_ok(Cin, Cout)) return 0;
+    const ConvAlgo a = conv_algo(algo);
+    switch (a.family) {
+        case FAMILY_BF16: return sstem::pack_group_entry_bf16((int)Cin, (int)Cout, entry16);
+        case FAMILY_SPLIT:
+            return a.f16 ? sstem::pack_group_entry_split_f16((int)Cin, (int)Cout, entry16)
+                         : sstem::pack_group_entry_split((int)Cin, (int)Cout, a.pieces, entry16);
+        case FAMILY_FP32: return sstem::pack_group_entry((int)Cin, (int)Cout, entry16);
+        default: return 0;
+    }
 }
 
 int sstem_conv3x3_pack_weights_group_f32(const int64_t* table, int64_t n_entries, int64_t total_blocks, int algo, void* stream)
@@ -352,17 +460,18 @@ int sstem_conv3x3_pack_weights_group_f32(const int64_t* table, int64_t n_entries
     if (n_entries < 0 || total_blocks < 0 || n_entries > (1 << 20)) return fail(SSTEM_ERR_BAD_SHAPE, "pack group: bad counts");
     if (n_entries == 0) return SSTEM_OK;
     if (!table) return fail(SSTEM_ERR_NULL_POINTER, "pack group: null table");
+    const ConvAlgo a = conv_algo(algo);
+    hipStream_t s = static_cast<hipStream_t>(stream);
     hipError_t e;
-    if (algo == SSTEM_CONV_MFMA_BF16)
-        e = sstem::launch_pack_weights_3x3_bf16_group(table, (int)n_entries, total_blocks, static_cast<hipStream_t>(stream));
-    else if (split_pieces_of(algo))
-        e = sstem::launch_pack_weights_3x3_split_group(table, (int)n_entries, total_blocks, split_pieces_of(algo), static_cast<hipStream_t>(stream));
-    else if (algo == SSTEM_CONV_MFMA)
-        e = sstem::launch_pack_weights_3x3_group(table, (int)n_entries, total_blocks, static_cast<hipStream_t>(stream));
+    if (a.family == FAMILY_BF16)
+        e = sstem::launch_pack_weights_3x3_bf16_group(table, (int)n_entries, total_blocks, s);
+    else if (a.split_bf16())                                     // the fp16 id has its own group entry, below
+        e = sstem::launch_pack_weights_3x3_split_group(table, (int)n_entries, total_blocks, a.pieces, s);
+    else if (a.family == FAMILY_FP32)
+        e = sstem::launch_pack_weights_3x3_group(table, (int)n_entries, total_blocks, s);
     else
         return fail(SSTEM_ERR_UNSUPPORTED, "pack group: an explicit MFMA algorithm id is needed");
-    if (e != hipSuccess) return hip_fail("pack group launch", e);
-    return SSTEM_OK;
+    return launched("pack group launch", e);
 }
 
 int sstem_conv3x3_pack_weights_group_f16(const int64_t* table, int64_t n_entries, int64_t total_blocks, int64_t bound_blocks, float* bounds,
@@ -373,21 +482,19 @@ int sstem_conv3x3_pack_weights_group_f16(const int64_t* table, int64_t n_entries
     if (!table || !bounds) return fail(SSTEM_ERR_NULL_POINTER, "pack group f16: null table / bounds");
     const hipError_t e = sstem::launch_pack_weights_3x3_split_f16_group(table, (int)n_entries, total_blocks, bound_blocks, bounds,
                                                                         static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("pack group f16 launch", e);
-    return SSTEM_OK;
+    return launched("pack group f16 launch", e);
 }
 
 int64_t sstem_conv3x3_forward_workspace_floats_algo(int64_t N, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int algo)
 {
     if (!conv_sizes_ok(N, Cin, H, W, Cout) || Cin <= 0 || Cout <= 0) return 0;
-    if (algo == SSTEM_CONV_MFMA_BF16)
-        return sstem::conv3x3_bf16_forward_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout);
-    if (split_pieces_of(algo))
-        return sstem::conv3x3_split_forward_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout, split_pieces_of(algo));
-    if (algo == SSTEM_CONV_MFMA_F16X3)
-        return sstem::conv3x3_split_forward_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout, 2, 1);
-    if (algo == SSTEM_CONV_DIRECT) return 0;
-    return sstem::conv3x3_forward_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout);
+    const ConvAlgo a = conv_algo(algo);
+    switch (a.family) {
+        case FAMILY_BF16: return sstem::conv3x3_bf16_forward_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout);
+        case FAMILY_SPLIT: return sstem::conv3x3_split_forward_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout, a.pieces, a.f16);
+        case FAMILY_DIRECT: return 0;
+        default: return sstem::conv3x3_forward_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout);      // AUTO and any other id: the fp32 plan
+    }
 }
 
 int sstem_conv2d_forward_f32(const float* input, const float* weight, const float* bias,
@@ -403,7 +510,7 @@ int sstem_conv2d_forward_f32(const float* input, const float* weight, const floa
 
 int64_t sstem_conv_bn_partials(int64_t N, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int KH, int KW, int transposed, int algo)
 {
-    if (!conv_sizes_ok(N, Cin, transposed ? 2 * H : H, transposed ? 2 * W : W, Cout) || N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
+    if (!conv_sizes_positive(N, Cin, transposed ? 2 * H : H, transposed ? 2 * W : W, Cout)) return 0;
     if (KH != 3 || KW != 3) return 0;
     if (algo == SSTEM_CONV_AUTO) algo = (N * ((Cout + 31) / 32) < 65536) ? SSTEM_CONV_MFMA : SSTEM_CONV_DIRECT;
     if (algo != SSTEM_CONV_MFMA) return 0;
@@ -423,7 +530,7 @@ int sstem_conv2d_forward_ex_f32(const float* input, const float* weight, const f
         return fail(SSTEM_ERR_BAD_SHAPE, "conv2d: bad shape");
     if (2 * pad_h != KH - 1 || 2 * pad_w != KW - 1)
         return fail(SSTEM_ERR_UNSUPPORTED, "conv2d: only stride-1 'same' padding is supported");
-    if (act < 0 || act > 2) return fail(SSTEM_ERR_UNSUPPORTED, "conv2d: unknown activation id");
+    if (int rc = check_act("conv2d", act)) return rc;
     if (N == 0 || Cout == 0 || H == 0 || W == 0) return SSTEM_OK;
     if (!input || !weight || !output) return fail(SSTEM_ERR_NULL_POINTER, "conv2d: null tensor pointer");
     const bool is3x3 = (KH == 3 && KW == 3);
@@ -431,8 +538,9 @@ int sstem_conv2d_forward_ex_f32(const float* input, const float* weight, const f
     if (weight_transposed < 0 || weight_transposed > 3) return fail(SSTEM_ERR_UNSUPPORTED, "conv2d: unknown weight_transposed flags");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (algo == SSTEM_CONV_AUTO) algo = (is3x3 && Cin > 0 && N * ((Cout + 31) / 32) < 65536) ? SSTEM_CONV_MFMA : SSTEM_CONV_DIRECT;
+    const ConvAlgo a = conv_algo(algo);
     hipError_t e;
-    if (algo == SSTEM_CONV_MFMA) {
+    if (a.family == FAMILY_FP32) {
         if (!is3x3 || Cin == 0) return fail(SSTEM_ERR_UNSUPPORTED, "conv2d: the MFMA kernel is 3x3/s1/p1 only");
         const int64_t need = sstem::conv3x3_workspace_floats((int)Cin, (int)Cout);
         if (!workspace || workspace_floats < need)
@@ -443,19 +551,18 @@ int sstem_conv2d_forward_ex_f32(const float* input, const float* weight, const f
             return fail(SSTEM_ERR_BAD_SHAPE, "conv2d: bn_partials need the full workspace (sstem_conv3x3_forward_workspace_floats)");
         e = sstem::launch_conv3x3_mfma(input, weight, bias, scale, shift, output, workspace, workspace_floats, (int)N,
                                        (int)Cin, (int)H, (int)W, (int)Cout, act, slope, weight_transposed & 3, s, ex);
-    } else if (split_pieces_of(algo)) {
-        const int pieces = split_pieces_of(algo);
+    } else if (a.split_bf16()) {                                 // the fp16 id is for sstem_conv3x3_forward_scaled_f32 only
         if (!is3x3 || Cin == 0) return fail(SSTEM_ERR_UNSUPPORTED, "conv2d: the split-bf16 MFMA kernel is 3x3/s1/p1 only");
         if (bn_partials) return fail(SSTEM_ERR_UNSUPPORTED, "conv2d: bn_partials need the fp32 3x3 MFMA kernel (SSTEM_CONV_MFMA)");
         if (!sstem::conv3x3_split_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout))
             return fail(SSTEM_ERR_UNSUPPORTED, "conv2d: the split-bf16 MFMA kernel needs a channel plane (W % 4 == 0) or a whole input image below 2 GiB");
-        if (!workspace || workspace_floats < sstem::conv3x3_split_packed_floats((int)Cin, (int)Cout, pieces))
+        if (!workspace || workspace_floats < sstem::conv3x3_split_packed_floats((int)Cin, (int)Cout, a.pieces))
             return fail(SSTEM_ERR_BAD_SHAPE, "conv2d: workspace too small (see sstem_conv3x3_forward_workspace_floats_algo)");
         e = sstem::launch_conv3x3_split_mfma(input, weight, bias, scale, shift, output, workspace, workspace_floats, (int)N, (int)Cin,
-                                             (int)H, (int)W, (int)Cout, act, slope, weight_transposed & 3, pieces, s, ex);
+                                             (int)H, (int)W, (int)Cout, act, slope, weight_transposed & 3, a.pieces, s, ex);
     } else if (residual || bn_partials) {
         return fail(SSTEM_ERR_UNSUPPORTED, "conv2d: residual / bn_partials need the fp32 3x3 MFMA kernel (SSTEM_CONV_MFMA)");
-    } else if (algo == SSTEM_CONV_MFMA_BF16) {
+    } else if (a.family == FAMILY_BF16) {
         if (!is3x3 || Cin == 0) return fail(SSTEM_ERR_UNSUPPORTED, "conv2d: the bf16 MFMA kernel is 3x3/s1/p1 only");
         if (!sstem::conv3x3_bf16_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout))
             return fail(SSTEM_ERR_UNSUPPORTED, "conv2d: the bf16 MFMA kernel needs a channel plane (W % 4 == 0) or a whole input image below 2 GiB");
@@ -463,15 +570,14 @@ int sstem_conv2d_forward_ex_f32(const float* input, const float* weight, const f
             return fail(SSTEM_ERR_BAD_SHAPE, "conv2d: workspace too small (see sstem_conv3x3_forward_workspace_floats_algo)");
         e = sstem::launch_conv3x3_bf16_mfma(input, weight, bias, scale, shift, output, workspace, workspace_floats, (int)N,
                                             (int)Cin, (int)H, (int)W, (int)Cout, act, slope, weight_transposed & 3, s);
-    } else if (algo == SSTEM_CONV_DIRECT) {
+    } else if (a.family == FAMILY_DIRECT) {
         if (weight_transposed) return fail(SSTEM_ERR_UNSUPPORTED, "conv2d: direct kernel takes plain [Cout,Cin,KH,KW] weights only");
         e = sstem::launch_conv2d_direct(input, weight, bias, scale, shift, output, (int)N, (int)Cin, (int)H,
                                         (int)W, (int)Cout, KH, KW, pad_h, pad_w, act, slope, s);
     } else {
         return fail(SSTEM_ERR_UNSUPPORTED, "conv2d: unknown algorithm id");
     }
-    if (e != hipSuccess) return hip_fail("conv2d launch", e);
-    return SSTEM_OK;
+    return launched("conv2d launch", e);
 }
 
 int sstem_conv3x3_forward_masked_f32(const float* input, const uint8_t* input_mask, const float* weight, const float* bias,
@@ -479,23 +585,17 @@ int sstem_conv3x3_forward_masked_f32(const float* input, const uint8_t* input_ma
                                      float* workspace, int64_t workspace_floats, int64_t N, int64_t Cin, int64_t H, int64_t W,
                                      int64_t Cout, int weight_flags, int act, float slope, void* stream, int algo)
 {
-    if (!conv_sizes_ok(N, Cin, H, W, Cout) || Cin <= 0) return fail(SSTEM_ERR_BAD_SHAPE, "conv3x3 masked: bad shape");
-    if (act < 0 || act > 2) return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 masked: unknown activation id");
-    if (weight_flags < 0 || weight_flags > 3) return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 masked: unknown weight flags");
-    const int pieces = split_pieces_of(algo);
-    if (!pieces) return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 masked: a split-bf16 id is needed (SSTEM_CONV_MFMA_BF16X6 / _BF16X3)");
+    const char* what = "conv3x3 masked";
+    if (!conv_sizes_ok(N, Cin, H, W, Cout) || Cin <= 0) return fail(SSTEM_ERR_BAD_SHAPE, "%s: bad shape", what);
+    if (int rc = check_act(what, act)) return rc;
+    if (int rc = check_weight_flags(what, weight_flags)) return rc;
+    const ConvAlgo a = conv_algo(algo);
+    if (!a.split_bf16()) return fail(SSTEM_ERR_UNSUPPORTED, "%s: a split-bf16 id is needed (SSTEM_CONV_MFMA_BF16X6 / _BF16X3)", what);
     if (N == 0 || Cout == 0 || H == 0 || W == 0) return SSTEM_OK;
-    if (!input || !weight || !output) return fail(SSTEM_ERR_NULL_POINTER, "conv3x3 masked: null tensor pointer");
-    if (!sstem::conv3x3_split_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout))
-        return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 masked: outside the split kernel's range");
-    if (!workspace || workspace_floats < sstem::conv3x3_split_packed_floats((int)Cin, (int)Cout, pieces))
-        return fail(SSTEM_ERR_BAD_SHAPE, "conv3x3 masked: workspace too small (see sstem_conv3x3_forward_workspace_floats_algo)");
+    if (!input || !weight || !output) return fail(SSTEM_ERR_NULL_POINTER, "%s: null tensor pointer", what);
     const sstem::ConvExtra ex{nullptr, 1.f, nullptr, 0, input_mask, output_mask};
-    const hipError_t e = sstem::launch_conv3x3_split_mfma(input, weight, bias, scale, shift, output, workspace, workspace_floats, (int)N,
-                                                          (int)Cin, (int)H, (int)W, (int)Cout, act, slope, weight_flags,
-                                                          pieces, static_cast<hipStream_t>(stream), ex);
-    if (e != hipSuccess) return hip_fail("conv3x3 masked launch", e);
-    return SSTEM_OK;
+    return split_forward(what, "", input, weight, bias, scale, shift, output, workspace, workspace_floats, N, Cin, H, W, Cout, weight_flags, act,
+                         slope, a.pieces, ex, stream);
 }
 
 int64_t sstem_amax_word_floats(void) { return 1024; }
@@ -506,8 +606,7 @@ int sstem_amax_f32(const float* x, int64_t n, float* word, void* stream)
     if (n == 0) return SSTEM_OK;
     if (!x || !word) return fail(SSTEM_ERR_NULL_POINTER, "amax: null pointer");
     const hipError_t e = sstem::launch_amax(x, n, word, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("amax launch", e);
-    return SSTEM_OK;
+    return launched("amax launch", e);
 }
 
 int sstem_conv3x3_forward_scaled_f32(const float* input, const float* input_amax, const float* weight, const float* bias,
@@ -543,8 +642,8 @@ int sstem_conv3x3_forward_scaled_strided_f32(const float* input, const float* in
                                            "of 32, Cin a multiple of 16, W a multiple of 4 and one output image below 4 GiB");
     if (output_layout == SSTEM_LAYOUT_ROW_SEGMENTS && (residual || H * ((W + 63) / 64) * Cout * 256 >= ((int64_t)1 << 32)))
         return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 scaled: the row-segment output takes no residual and one image of it must stay below 4 GiB");
-    if (act < 0 || act > 2) return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 scaled: unknown activation id");
-    if (weight_flags < 0 || weight_flags > 3) return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 scaled: unknown weight flags");
+    if (int rc = check_act("conv3x3 scaled", act)) return rc;
+    if (int rc = check_weight_flags("conv3x3 scaled", weight_flags)) return rc;
     if (algo == SSTEM_CONV_DIRECT) {
         // the streaming fp32 kernel for a handful of output channels: exact fp32 products, so no input bound is read; it leaves the
         // output's bound like the split ids do (a link of an fp16 chain)
@@ -557,28 +656,19 @@ int sstem_conv3x3_forward_scaled_strided_f32(const float* input, const float* in
             return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 scaled: SSTEM_CONV_DIRECT here is the streaming kernel (sstem_conv3x3_stream_small_supported)");
         const hipError_t e = sstem::launch_conv3x3_stream_small(input, weight, bias, scale, shift, output, (int)N, (int)Cin, (int)H, (int)W,
                                                                 (int)Cout, act, slope, output_amax, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return hip_fail("conv3x3 scaled launch (streaming kernel)", e);
-        return SSTEM_OK;
+        return launched("conv3x3 scaled launch (streaming kernel)", e);
     }
-    const int pieces = scaled_pieces_of(algo);
-    const int f16 = algo == SSTEM_CONV_MFMA_F16X3 ? 1 : 0;
-    if (!pieces) return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 scaled: a split id (SSTEM_CONV_MFMA_F16X3 / _BF16X6 / _BF16X3) or SSTEM_CONV_DIRECT is needed");
+    const ConvAlgo a = conv_algo(algo);
+    if (a.family != FAMILY_SPLIT)
+        return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 scaled: a split id (SSTEM_CONV_MFMA_F16X3 / _BF16X6 / _BF16X3) or SSTEM_CONV_DIRECT is needed");
     if (N == 0 || Cout == 0 || H == 0 || W == 0) return SSTEM_OK;
     if (!input || !weight || (!output && !pooled_output)) return fail(SSTEM_ERR_NULL_POINTER, "conv3x3 scaled: null tensor pointer");
-    if (f16 && !input_amax) return fail(SSTEM_ERR_NULL_POINTER, "conv3x3 scaled: SSTEM_CONV_MFMA_F16X3 needs the input's amax word (sstem_amax_f32)");
-    if (!sstem::conv3x3_split_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout) ||
-        (f16 && !sstem::conv3x3_split_f16_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout)))
-        return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 scaled: outside the split kernel's range (sstem_conv3x3_algo_supported)");
-    if (!workspace || workspace_floats < sstem::conv3x3_split_packed_floats((int)Cin, (int)Cout, pieces, f16))
-        return fail(SSTEM_ERR_BAD_SHAPE, "conv3x3 scaled: workspace too small (see sstem_conv3x3_forward_workspace_floats_algo)");
-    const sstem::ConvExtra ex{residual, residual_scale, nullptr, 0, nullptr, nullptr, input_amax, output_amax, f16,
+    if (a.f16 && !input_amax) return fail(SSTEM_ERR_NULL_POINTER, "conv3x3 scaled: SSTEM_CONV_MFMA_F16X3 needs the input's amax word (sstem_amax_f32)");
+    const sstem::ConvExtra ex{residual, residual_scale, nullptr, 0, nullptr, nullptr, input_amax, output_amax, a.f16,
                               output_layout == SSTEM_LAYOUT_ROW_SEGMENTS ? 1 : (output_layout == SSTEM_LAYOUT_CONVT_PARITY ? 2 : 0),
                               output_image_stride == Cout * H * W ? 0 : output_image_stride, pooled_output, pooled_output ? pool_kind : 0};
-    const hipError_t e = sstem::launch_conv3x3_split_mfma(input, weight, bias, scale, shift, output, workspace, workspace_floats, (int)N,
-                                                          (int)Cin, (int)H, (int)W, (int)Cout, act, slope, weight_flags,
-                                                          pieces, static_cast<hipStream_t>(stream), ex);
-    if (e != hipSuccess) return hip_fail("conv3x3 scaled launch", e);
-    return SSTEM_OK;
+    return split_forward("conv3x3 scaled", " (sstem_conv3x3_algo_supported)", input, weight, bias, scale, shift, output, workspace,
+                         workspace_floats, N, Cin, H, W, Cout, weight_flags, act, slope, a.pieces, ex, stream);
 }
 
 int sstem_conv3x3_forward_scaled_masked_f32(const float* input, const float* input_amax, const uint8_t* input_mask, const float* weight,
@@ -586,45 +676,27 @@ int sstem_conv3x3_forward_scaled_masked_f32(const float* input, const float* inp
                                             uint8_t* output_mask, float* workspace, int64_t workspace_floats, int64_t N, int64_t Cin,
                                             int64_t H, int64_t W, int64_t Cout, int weight_flags, int act, float slope, void* stream)
 {
-    if (!conv_sizes_ok(N, Cin, H, W, Cout) || Cin <= 0) return fail(SSTEM_ERR_BAD_SHAPE, "conv3x3 scaled masked: bad shape");
-    if (act < 0 || act > 2) return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 scaled masked: unknown activation id");
-    if (weight_flags < 0 || weight_flags > 3) return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 scaled masked: unknown weight flags");
+    const char* what = "conv3x3 scaled masked";
+    if (!conv_sizes_ok(N, Cin, H, W, Cout) || Cin <= 0) return fail(SSTEM_ERR_BAD_SHAPE, "%s: bad shape", what);
+    if (int rc = check_act(what, act)) return rc;
+    if (int rc = check_weight_flags(what, weight_flags)) return rc;
     if (N == 0 || Cout == 0 || H == 0 || W == 0) return SSTEM_OK;
-    if (!input || !input_amax || !weight || !output) return fail(SSTEM_ERR_NULL_POINTER, "conv3x3 scaled masked: null tensor pointer");
+    if (!input || !input_amax || !weight || !output) return fail(SSTEM_ERR_NULL_POINTER, "%s: null tensor pointer", what);
     if ((input_mask || output_mask) && (W % 4 != 0 || (reinterpret_cast<uintptr_t>(input) & 15) != 0))
-        return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 scaled masked: the masked fp16 instances take W % 4 == 0 and a 16-byte aligned input");
-    if (!sstem::conv3x3_split_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout) ||
-        !sstem::conv3x3_split_f16_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout))
-        return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 scaled masked: outside the split kernel's range (sstem_conv3x3_algo_supported)");
-    if (!workspace || workspace_floats < sstem::conv3x3_split_packed_floats((int)Cin, (int)Cout, 2, 1))
-        return fail(SSTEM_ERR_BAD_SHAPE, "conv3x3 scaled masked: workspace too small (see sstem_conv3x3_forward_workspace_floats_algo)");
+        return fail(SSTEM_ERR_UNSUPPORTED, "%s: the masked fp16 instances take W %% 4 == 0 and a 16-byte aligned input", what);
     const sstem::ConvExtra ex{nullptr, 1.f, nullptr, 0, input_mask, output_mask, input_amax, output_amax, 1, 0, 0, nullptr, 0};
-    const hipError_t e = sstem::launch_conv3x3_split_mfma(input, weight, bias, scale, shift, output, workspace, workspace_floats, (int)N,
-                                                          (int)Cin, (int)H, (int)W, (int)Cout, act, slope, weight_flags, 2,
-                                                          static_cast<hipStream_t>(stream), ex);
-    if (e != hipSuccess) return hip_fail("conv3x3 scaled masked launch", e);
-    return SSTEM_OK;
+    return split_forward(what, " (sstem_conv3x3_algo_supported)", input, weight, bias, scale, shift, output, workspace, workspace_floats, N, Cin,
+                         H, W, Cout, weight_flags, act, slope, 2, ex, stream);
 }
 
 int sstem_conv3x3_backward_weight_masked_f32(const float* input, const float* grad_output, const uint8_t* grad_mask, float* grad_weight,
                                              float* grad_bias, float* workspace, int64_t workspace_floats, int64_t N, int64_t Cin,
                                              int64_t H, int64_t W, int64_t Cout, int accumulate, void* stream, int algo)
 {
-    if (!conv_sizes_ok(N, Cin, H, W, Cout) || N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0)
-        return fail(SSTEM_ERR_BAD_SHAPE, "conv3x3 wgrad masked: bad shape");
-    const int pieces = split_pieces_of(algo);
-    if (!pieces) return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 wgrad masked: a split-bf16 id is needed (SSTEM_CONV_MFMA_BF16X6 / _BF16X3)");
-    if (!input || !grad_output || !grad_weight) return fail(SSTEM_ERR_NULL_POINTER, "conv3x3 wgrad masked: null tensor pointer");
-    if (Cin * Cout >= ((int64_t)1 << 31)) return fail(SSTEM_ERR_BAD_SHAPE, "conv3x3 wgrad masked: Cin*Cout too large");
-    if (!sstem::conv3x3_wgrad_split_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout))
-        return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 wgrad masked: outside the split kernel's range");
-    if (!workspace || workspace_floats < sstem::conv3x3_wgrad_split_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout))
-        return fail(SSTEM_ERR_BAD_SHAPE, "conv3x3 wgrad masked: workspace too small (see sstem_conv3x3_wgrad_workspace_floats_algo)");
-    const hipError_t e = sstem::launch_conv3x3_wgrad_split_mfma(input, grad_output, grad_weight, grad_bias, workspace, (int)N, (int)Cin,
-                                                                (int)H, (int)W, (int)Cout, pieces, static_cast<hipStream_t>(stream),
-                                                                wgrad_flags(accumulate), grad_mask);
-    if (e != hipSuccess) return hip_fail("conv3x3 wgrad masked launch", e);
-    return SSTEM_OK;
+    const ConvAlgo a = conv_algo(algo);
+    return backward_weight_split("conv3x3 wgrad masked", a.split_bf16() ? a.pieces : 0, !input || !grad_output || !grad_weight, input, nullptr,
+                                 grad_output, nullptr, grad_mask, grad_weight, grad_bias, workspace, workspace_floats, N, Cin, H, W, Cout,
+                                 accumulate, stream);
 }
 
 int sstem_conv3x3_backward_weight_scaled_masked_f32(const float* input, const float* input_amax, const float* grad_output,
@@ -632,29 +704,19 @@ int sstem_conv3x3_backward_weight_scaled_masked_f32(const float* input, const fl
                                                     float* workspace, int64_t workspace_floats, int64_t N, int64_t Cin, int64_t H,
                                                     int64_t W, int64_t Cout, int accumulate, void* stream)
 {
-    if (!conv_sizes_ok(N, Cin, H, W, Cout) || N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0)
-        return fail(SSTEM_ERR_BAD_SHAPE, "conv3x3 wgrad scaled: bad shape");
-    if (!input || !input_amax || !grad_output || !grad_amax || !grad_weight)
-        return fail(SSTEM_ERR_NULL_POINTER, "conv3x3 wgrad scaled: null tensor pointer");
-    if (Cin * Cout >= ((int64_t)1 << 31)) return fail(SSTEM_ERR_BAD_SHAPE, "conv3x3 wgrad scaled: Cin*Cout too large");
-    if (!sstem::conv3x3_wgrad_split_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout))
-        return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 wgrad scaled: outside the split kernel's range");
-    if (!workspace || workspace_floats < sstem::conv3x3_wgrad_split_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout))
-        return fail(SSTEM_ERR_BAD_SHAPE, "conv3x3 wgrad scaled: workspace too small (see sstem_conv3x3_wgrad_workspace_floats_algo)");
-    const hipError_t e = sstem::launch_conv3x3_wgrad_split_mfma(input, grad_output, grad_weight, grad_bias, workspace, (int)N, (int)Cin,
-                                                                (int)H, (int)W, (int)Cout, 2, static_cast<hipStream_t>(stream),
-                                                                wgrad_flags(accumulate), grad_mask, input_amax, grad_amax);
-    if (e != hipSuccess) return hip_fail("conv3x3 wgrad scaled launch", e);
-    return SSTEM_OK;
+    return backward_weight_split("conv3x3 wgrad scaled", 2, !input || !input_amax || !grad_output || !grad_amax || !grad_weight, input,
+                                 input_amax, grad_output, grad_amax, grad_mask, grad_weight, grad_bias, workspace, workspace_floats, N, Cin, H,
+                                 W, Cout, accumulate, stream);
 }
 
 int sstem_conv3x3_algo_supported(int64_t N, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int algo)
 {
-    if (!conv_sizes_ok(N, Cin, H, W, Cout) || N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
-    if (algo == SSTEM_CONV_DIRECT) return 1;
-    if (algo == SSTEM_CONV_MFMA_F16X3) return sstem::conv3x3_split_f16_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout) ? 1 : 0;
-    if (algo == SSTEM_CONV_MFMA_BF16 || scaled_pieces_of(algo)) return sstem::conv3x3_bf16_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout) ? 1 : 0;
-    if (algo == SSTEM_CONV_MFMA || algo == SSTEM_CONV_AUTO) return N * ((Cout + 31) / 32) < 65536 ? 1 : 0;
+    if (!conv_sizes_positive(N, Cin, H, W, Cout)) return 0;
+    const ConvAlgo a = conv_algo(algo);
+    if (a.family == FAMILY_DIRECT) return 1;
+    if (a.family == FAMILY_SPLIT && a.f16) return sstem::conv3x3_split_f16_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout) ? 1 : 0;
+    if (a.family == FAMILY_BF16 || a.family == FAMILY_SPLIT) return sstem::conv3x3_bf16_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout) ? 1 : 0;
+    if (a.family == FAMILY_FP32 || algo == SSTEM_CONV_AUTO) return N * ((Cout + 31) / 32) < 65536 ? 1 : 0;
     return 0;
 }
 
@@ -670,22 +732,21 @@ int sstem_conv3x3_first_layer_u8(const uint8_t* frames, const float* weight, con
     if (!sstem_conv3x3_first_layer_u8_supported(N, H, W, Cout))
         return fail(SSTEM_ERR_UNSUPPORTED, "first layer from uint8 frames: Conv2d(6 -> 6), W % 4 == 0, 2*H*W < 2^31");
     if (!frames || !weight || !output) return fail(SSTEM_ERR_NULL_POINTER, "first layer from uint8 frames: null pointer");
-    if (act < 0 || act > 2) return fail(SSTEM_ERR_UNSUPPORTED, "first layer from uint8 frames: unknown activation");
+    if (!act_ok(act)) return fail(SSTEM_ERR_UNSUPPORTED, "first layer from uint8 frames: unknown activation");
     hipError_t e = sstem::launch_conv3x3_first_u8(frames, weight, bias, output, planes, (int)N, (int)H, (int)W, (int)Cout, act, slope,
                                                   output_amax, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("first layer from uint8 frames launch", e);
-    return SSTEM_OK;
+    return launched("first layer from uint8 frames launch", e);
 }
 
 int sstem_conv3x3_stream_small_supported(int64_t N, int64_t Cin, int64_t H, int64_t W, int64_t Cout)
 {
-    if (!conv_sizes_ok(N, Cin, H, W, Cout) || N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
+    if (!conv_sizes_positive(N, Cin, H, W, Cout)) return 0;
     return sstem::conv3x3_stream_small_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout) ? 1 : 0;
 }
 
 int sstem_conv3x3_bf16io_supported(int64_t N, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int output_bf16)
 {
-    if (!conv_sizes_ok(N, Cin, H, W, Cout) || N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
+    if (!conv_sizes_positive(N, Cin, H, W, Cout)) return 0;
     return sstem::conv3x3_bf16_io_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout, output_bf16) ? 1 : 0;
 }
 
@@ -694,21 +755,8 @@ int sstem_conv3x3_forward_bf16io(const void* input, int input_bf16, const float*
                                  int64_t N, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int weight_flags, int act, float slope,
                                  void* stream)
 {
-    if (!conv_sizes_ok(N, Cin, H, W, Cout)) return fail(SSTEM_ERR_BAD_SHAPE, "conv3x3 bf16io: bad shape");
-    if (act < 0 || act > 2) return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 bf16io: unknown activation id");
-    if (weight_flags < 0 || weight_flags > 3) return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 bf16io: unknown weight flags");
-    if (N == 0 || Cout == 0 || H == 0 || W == 0) return SSTEM_OK;
-    if (!input || !weight || !output) return fail(SSTEM_ERR_NULL_POINTER, "conv3x3 bf16io: null tensor pointer");
-    if (Cin == 0 || !sstem::conv3x3_bf16_io_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout, output_bf16))
-        return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 bf16io: needs W % 4 == 0, a channel plane below 2 GiB and, for a bf16 output, an unsplit launch "
-                                           "(sstem_conv3x3_bf16io_supported)");
-    if (!workspace || workspace_floats < sstem::conv3x3_bf16_packed_floats((int)Cin, (int)Cout))
-        return fail(SSTEM_ERR_BAD_SHAPE, "conv3x3 bf16io: workspace too small (see sstem_conv3x3_forward_workspace_floats_algo)");
-    hipError_t e = sstem::launch_conv3x3_bf16_mfma_io(input, input_bf16 ? 1 : 0, weight, bias, scale, shift, output, output_bf16 ? 1 : 0,
-                                                      workspace, workspace_floats, (int)N, (int)Cin, (int)H, (int)W, (int)Cout, act, slope,
-                                                      weight_flags, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("conv3x3 bf16io launch", e);
-    return SSTEM_OK;
+    return forward_bf16io("conv3x3 bf16io", input, input_bf16, nullptr, weight, bias, scale, shift, output, output_bf16, nullptr, workspace,
+                          workspace_floats, N, Cin, H, W, Cout, weight_flags, act, slope, stream);
 }
 
 int sstem_conv3x3_forward_bf16io_masked(const void* input, int input_bf16, const uint8_t* input_mask, const float* weight, const float* bias,
@@ -716,32 +764,15 @@ int sstem_conv3x3_forward_bf16io_masked(const void* input, int input_bf16, const
                                         float* workspace, int64_t workspace_floats, int64_t N, int64_t Cin, int64_t H, int64_t W,
                                         int64_t Cout, int weight_flags, int act, float slope, void* stream)
 {
-    if (!conv_sizes_ok(N, Cin, H, W, Cout)) return fail(SSTEM_ERR_BAD_SHAPE, "conv3x3 bf16io masked: bad shape");
-    if (act < 0 || act > 2) return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 bf16io masked: unknown activation id");
-    if (weight_flags < 0 || weight_flags > 3) return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 bf16io masked: unknown weight flags");
-    if (N == 0 || Cout == 0 || H == 0 || W == 0) return SSTEM_OK;
-    if (!input || !weight || !output) return fail(SSTEM_ERR_NULL_POINTER, "conv3x3 bf16io masked: null tensor pointer");
-    if (input_bf16 && input_mask)
-        return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 bf16io masked: input_mask needs an fp32 input tensor");
-    if ((input_mask || output_mask) && (reinterpret_cast<uintptr_t>(input) & 15) != 0)
-        return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 bf16io masked: the masks need a 16-byte aligned input");
-    if (Cin == 0 || !sstem::conv3x3_bf16_io_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout, output_bf16))
-        return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 bf16io masked: needs W % 4 == 0, a channel plane below 2 GiB and, for a bf16 output, an "
-                                           "unsplit launch (sstem_conv3x3_bf16io_supported)");
-    if (!workspace || workspace_floats < sstem::conv3x3_bf16_packed_floats((int)Cin, (int)Cout))
-        return fail(SSTEM_ERR_BAD_SHAPE, "conv3x3 bf16io masked: workspace too small (see sstem_conv3x3_forward_workspace_floats_algo)");
-    hipError_t e = sstem::launch_conv3x3_bf16_mfma_io(input, input_bf16 ? 1 : 0, weight, bias, scale, shift, output, output_bf16 ? 1 : 0,
-                                                      workspace, workspace_floats, (int)N, (int)Cin, (int)H, (int)W, (int)Cout, act, slope,
-                                                      weight_flags, static_cast<hipStream_t>(stream), input_mask, output_mask);
-    if (e != hipSuccess) return hip_fail("conv3x3 bf16io masked launch", e);
-    return SSTEM_OK;
+    return forward_bf16io("conv3x3 bf16io masked", input, input_bf16, input_mask, weight, bias, scale, shift, output, output_bf16, output_mask,
+                          workspace, workspace_floats, N, Cin, H, W, Cout, weight_flags, act, slope, stream);
 }
 
 int sstem_conv3x3_backward_weight_bf16_masked(const void* input, int input_bf16, const float* grad_output, const uint8_t* grad_mask,
                                               float* grad_weight, float* grad_bias, float* workspace, int64_t workspace_floats, int64_t N,
                                               int64_t Cin, int64_t H, int64_t W, int64_t Cout, int accumulate, void* stream)
 {
-    if (!conv_sizes_ok(N, Cin, H, W, Cout) || N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0)
+    if (!conv_sizes_positive(N, Cin, H, W, Cout))
         return fail(SSTEM_ERR_BAD_SHAPE, "conv3x3 wgrad bf16 masked: bad shape");
     if (!input || !grad_output || !grad_weight) return fail(SSTEM_ERR_NULL_POINTER, "conv3x3 wgrad bf16 masked: null tensor pointer");
     if (W % 4 != 0 || ((reinterpret_cast<uintptr_t>(input) | reinterpret_cast<uintptr_t>(grad_output)) & 15) != 0)
@@ -753,8 +784,7 @@ int sstem_conv3x3_backward_weight_bf16_masked(const void* input, int input_bf16,
     hipError_t e = sstem::launch_conv3x3_wgrad_bf16_mfma_in(input, input_bf16 ? 1 : 0, grad_output, grad_weight, grad_bias, workspace, (int)N,
                                                             (int)Cin, (int)H, (int)W, (int)Cout, static_cast<hipStream_t>(stream),
                                                             wgrad_flags(accumulate), grad_mask);
-    if (e != hipSuccess) return hip_fail("conv3x3 wgrad bf16 masked launch", e);
-    return SSTEM_OK;
+    return launched("conv3x3 wgrad bf16 masked launch", e);
 }
 
 int sstem_conv_transpose3x3s2_forward_f32(const float* input, const float* weight, const float* bias,
@@ -763,19 +793,18 @@ int sstem_conv_transpose3x3s2_forward_f32(const float* input, const float* weigh
                                           int act, float slope, void* stream)
 {
     if (!conv_sizes_ok(N, Cin, 2 * H, 2 * W, Cout)) return fail(SSTEM_ERR_BAD_SHAPE, "conv_transpose: bad shape");
-    if (act < 0 || act > 2) return fail(SSTEM_ERR_UNSUPPORTED, "conv_transpose: unknown activation id");
+    if (int rc = check_act("conv_transpose", act)) return rc;
     if (N == 0 || Cout == 0 || H == 0 || W == 0) return SSTEM_OK;
     if (!input || !weight || !output) return fail(SSTEM_ERR_NULL_POINTER, "conv_transpose: null tensor pointer");
     hipError_t e = sstem::launch_convT3x3s2_direct(input, weight, bias, scale, shift, output, (int)N, (int)Cin,
                                                    (int)H, (int)W, (int)Cout, act, slope,
                                                    static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("conv_transpose launch", e);
-    return SSTEM_OK;
+    return launched("conv_transpose launch", e);
 }
 
 int64_t sstem_conv_transpose3x3s2_workspace_floats(int64_t N, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int which)
 {
-    if (!conv_sizes_ok(N, Cin, 2 * H, 2 * W, Cout) || N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
+    if (!conv_sizes_positive(N, Cin, 2 * H, 2 * W, Cout)) return 0;
     const int64_t f = sstem::convT3x3s2_forward_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout);
     const int64_t d = sstem::convT3x3s2_dgrad_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout);
     const int64_t g = sstem::convT3x3s2_wgrad_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout);
@@ -793,7 +822,7 @@ int sstem_conv_transpose3x3s2_forward_ex_f32(const float* input, const float* we
                                              int weight_flags, int act, float slope, void* stream)
 {
     if (!conv_sizes_ok(N, Cin, 2 * H, 2 * W, Cout)) return fail(SSTEM_ERR_BAD_SHAPE, "conv_transpose: bad shape");
-    if (act < 0 || act > 2) return fail(SSTEM_ERR_UNSUPPORTED, "conv_transpose: unknown activation id");
+    if (int rc = check_act("conv_transpose", act)) return rc;
     if (weight_flags != 0 && weight_flags != SSTEM_CONV_WEIGHT_PREPACKED) return fail(SSTEM_ERR_UNSUPPORTED, "conv_transpose: unknown weight flags");
     if (N == 0 || Cout == 0 || H == 0 || W == 0) return SSTEM_OK;
     if (!input || !weight || !output) return fail(SSTEM_ERR_NULL_POINTER, "conv_transpose: null tensor pointer");
@@ -811,8 +840,7 @@ int sstem_conv_transpose3x3s2_forward_ex_f32(const float* input, const float* we
     hipError_t e = sstem::launch_convT3x3s2_mfma(input, weight, bias, scale, shift, output, workspace, workspace_floats, (int)N, (int)Cin,
                                                  (int)H, (int)W, (int)Cout, act, slope, weight_flags ? 1 : 0,
                                                  static_cast<hipStream_t>(stream), ex);
-    if (e != hipSuccess) return hip_fail("conv_transpose launch", e);
-    return SSTEM_OK;
+    return launched("conv_transpose launch", e);
 }
 
 int sstem_conv_transpose3x3s2_backward_ex_f32(const float* input, const float* weight, const float* grad_output,
@@ -856,17 +884,18 @@ int sstem_conv_transpose3x3s2_backward_ex_f32(const float* input, const float* w
 
 int64_t sstem_conv3x3_wgrad_workspace_floats(int64_t N, int64_t Cin, int64_t H, int64_t W, int64_t Cout)
 {
-    if (!conv_sizes_ok(N, Cin, H, W, Cout) || N == 0 || Cin == 0 || H == 0 || W == 0 || Cout == 0) return 0;
+    if (!conv_sizes_positive(N, Cin, H, W, Cout)) return 0;
     return sstem::conv3x3_wgrad_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout);
 }
 
 int64_t sstem_conv3x3_wgrad_workspace_floats_algo(int64_t N, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int algo)
 {
-    if (!conv_sizes_ok(N, Cin, H, W, Cout) || N == 0 || Cin == 0 || H == 0 || W == 0 || Cout == 0) return 0;
-    if (algo == SSTEM_CONV_MFMA_BF16) return sstem::conv3x3_wgrad_bf16_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout);
-    if ((split_pieces_of(algo) || algo == SSTEM_CONV_MFMA_F16X3) && sstem::conv3x3_wgrad_split_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout))
+    if (!conv_sizes_positive(N, Cin, H, W, Cout)) return 0;
+    const ConvAlgo a = conv_algo(algo);
+    if (a.family == FAMILY_BF16) return sstem::conv3x3_wgrad_bf16_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout);
+    if (a.family == FAMILY_SPLIT && sstem::conv3x3_wgrad_split_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout))
         return sstem::conv3x3_wgrad_split_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout);
-    if (algo == SSTEM_CONV_DIRECT) return 0;
+    if (a.family == FAMILY_DIRECT) return 0;
     return sstem::conv3x3_wgrad_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout);
 }
 
@@ -904,45 +933,44 @@ int sstem_conv2d_backward_weight_bias_ex_f32(const float* input, const float* gr
         if (accumulate) return SSTEM_OK;
         hipError_t e = hipMemsetAsync(grad_weight, 0, (size_t)Cout * Cin * KH * KW * sizeof(float), s);
         if (e == hipSuccess && grad_bias) e = hipMemsetAsync(grad_bias, 0, (size_t)Cout * sizeof(float), s);
-        if (e != hipSuccess) return hip_fail("conv2d wgrad memset", e);
-        return SSTEM_OK;
+        return launched("conv2d wgrad memset", e);
     }
     if (!input || !grad_output) return fail(SSTEM_ERR_NULL_POINTER, "conv2d wgrad: null tensor pointer");
     if (Cin * Cout >= ((int64_t)1 << 31)) return fail(SSTEM_ERR_BAD_SHAPE, "conv2d wgrad: Cin*Cout too large");
     const bool is3x3 = (KH == 3 && KW == 3);
     if (algo == SSTEM_CONV_AUTO) algo = is3x3 ? SSTEM_CONV_MFMA : SSTEM_CONV_DIRECT;
-    if (split_pieces_of(algo) && (!is3x3 || !sstem::conv3x3_wgrad_split_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout)))
-        algo = SSTEM_CONV_MFMA;                                 // outside the split kernel's range: the fp32 MFMA kernel
+    ConvAlgo a = conv_algo(algo);
+    if (a.split_bf16() && (!is3x3 || !sstem::conv3x3_wgrad_split_supported((int)N, (int)Cin, (int)H, (int)W, (int)Cout)))
+        a = conv_algo(SSTEM_CONV_MFMA);                         // outside the split kernel's range: the fp32 MFMA kernel
     hipError_t e;
-    if (algo == SSTEM_CONV_MFMA) {
+    if (a.family == FAMILY_FP32) {
         if (!is3x3) return fail(SSTEM_ERR_UNSUPPORTED, "conv2d wgrad: the MFMA kernel is 3x3 only");
         const int64_t need = sstem::conv3x3_wgrad_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout);
         if (!workspace || workspace_floats < need)
             return fail(SSTEM_ERR_BAD_SHAPE, "conv2d wgrad: workspace too small (see sstem_conv3x3_wgrad_workspace_floats)");
         e = sstem::launch_conv3x3_wgrad_mfma(input, grad_output, grad_weight, grad_bias, workspace, (int)N, (int)Cin, (int)H,
                                              (int)W, (int)Cout, s, wgrad_flags(accumulate));
-    } else if (split_pieces_of(algo)) {
+    } else if (a.split_bf16()) {
         const int64_t need = sstem::conv3x3_wgrad_split_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout);
         if (!workspace || workspace_floats < need)
             return fail(SSTEM_ERR_BAD_SHAPE, "conv2d wgrad: workspace too small (see sstem_conv3x3_wgrad_workspace_floats_algo)");
         e = sstem::launch_conv3x3_wgrad_split_mfma(input, grad_output, grad_weight, grad_bias, workspace, (int)N, (int)Cin, (int)H,
-                                                   (int)W, (int)Cout, split_pieces_of(algo), s, wgrad_flags(accumulate));
-    } else if (algo == SSTEM_CONV_MFMA_BF16) {
+                                                   (int)W, (int)Cout, a.pieces, s, wgrad_flags(accumulate));
+    } else if (a.family == FAMILY_BF16) {
         if (!is3x3) return fail(SSTEM_ERR_UNSUPPORTED, "conv2d wgrad: the bf16 MFMA kernel is 3x3 only");
         const int64_t need = sstem::conv3x3_wgrad_bf16_workspace_floats((int)N, (int)Cin, (int)H, (int)W, (int)Cout);
         if (!workspace || workspace_floats < need)
             return fail(SSTEM_ERR_BAD_SHAPE, "conv2d wgrad: workspace too small (see sstem_conv3x3_wgrad_workspace_floats_algo)");
         e = sstem::launch_conv3x3_wgrad_bf16_mfma(input, grad_output, grad_weight, grad_bias, workspace, (int)N, (int)Cin, (int)H,
                                                   (int)W, (int)Cout, s, wgrad_flags(accumulate));
-    } else if (algo == SSTEM_CONV_DIRECT) {
+    } else if (a.family == FAMILY_DIRECT) {
         if (grad_bias) return fail(SSTEM_ERR_UNSUPPORTED, "conv2d wgrad: the fused bias gradient needs the 3x3 MFMA kernel");
         e = sstem::launch_conv2d_wgrad_direct(input, grad_output, grad_weight, (int)N, (int)Cin, (int)H, (int)W,
                                               (int)Cout, KH, KW, pad_h, pad_w, s, accumulate ? 1 : 0);
     } else {
         return fail(SSTEM_ERR_UNSUPPORTED, "conv2d wgrad: unknown algorithm id");
     }
-    if (e != hipSuccess) return hip_fail("conv2d wgrad launch", e);
-    return SSTEM_OK;
+    return launched("conv2d wgrad launch", e);
 }
 
 int sstem_conv3x3_backward_weight_bf16in(const void* input_bf16, const float* grad_output, float* grad_weight, float* grad_bias,
@@ -957,7 +985,7 @@ int sstem_conv3x3_backward_weight_bf16in_ex(const void* input_bf16, const float*
                                             float* workspace, int64_t workspace_floats, int64_t N, int64_t Cin, int64_t H, int64_t W,
                                             int64_t Cout, int accumulate, void* stream)
 {
-    if (!conv_sizes_ok(N, Cin, H, W, Cout) || N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0)
+    if (!conv_sizes_positive(N, Cin, H, W, Cout))
         return fail(SSTEM_ERR_BAD_SHAPE, "conv3x3 wgrad bf16in: bad shape");
     if (!input_bf16 || !grad_output || !grad_weight) return fail(SSTEM_ERR_NULL_POINTER, "conv3x3 wgrad bf16in: null tensor pointer");
     if (W % 4 != 0) return fail(SSTEM_ERR_UNSUPPORTED, "conv3x3 wgrad bf16in: needs W % 4 == 0");
@@ -966,8 +994,7 @@ int sstem_conv3x3_backward_weight_bf16in_ex(const void* input_bf16, const float*
         return fail(SSTEM_ERR_BAD_SHAPE, "conv3x3 wgrad bf16in: workspace too small (see sstem_conv3x3_wgrad_workspace_floats_algo)");
     hipError_t e = sstem::launch_conv3x3_wgrad_bf16_mfma_in(input_bf16, 1, grad_output, grad_weight, grad_bias, workspace, (int)N, (int)Cin,
                                                             (int)H, (int)W, (int)Cout, static_cast<hipStream_t>(stream), wgrad_flags(accumulate));
-    if (e != hipSuccess) return hip_fail("conv3x3 wgrad bf16in launch", e);
-    return SSTEM_OK;
+    return launched("conv3x3 wgrad bf16in launch", e);
 }
 
 int sstem_conv_transpose3x3s2_backward_f32(const float* input, const float* weight,
@@ -1004,8 +1031,7 @@ int sstem_warp_bilinear_f32(const float* image, const float* flow, float* output
     if (!image || !flow || !output) return fail(SSTEM_ERR_NULL_POINTER, "warp: null tensor pointer");
     hipError_t e = sstem::launch_warp_bilinear(image, flow, output, (int)B, (int)C, (int)H, (int)W,
                                                static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("warp launch", e);
-    return SSTEM_OK;
+    return launched("warp launch", e);
 }
 
 // ---- uint8 edge + flat Adam (include/sstem_io.h) -----------------------------------------------
@@ -1015,8 +1041,7 @@ int sstem_gray_u8_to_f32(const uint8_t* image, float* output, int64_t npix, int6
     if (npix == 0 || replicas == 0) return SSTEM_OK;
     if (!image || !output) return fail(SSTEM_ERR_NULL_POINTER, "u8->f32: null pointer");
     hipError_t e = sstem::launch_gray_u8_to_f32(image, output, npix, (int)replicas, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("u8->f32 launch", e);
-    return SSTEM_OK;
+    return launched("u8->f32 launch", e);
 }
 
 static bool bn_sizes_ok(int64_t N, int64_t C, int64_t HW)
@@ -1064,7 +1089,7 @@ int sstem_batchnorm_train_forward_amax_f32(const float* x, const float* weight, 
                                            int act, float slope, void* stream)
 {
     if (!bn_sizes_ok(N, C, HW)) return fail(SSTEM_ERR_BAD_SHAPE, "batchnorm: bad shape");
-    if (act < 0 || act > 2) return fail(SSTEM_ERR_UNSUPPORTED, "batchnorm: unknown activation id");
+    if (int rc = check_act("batchnorm", act)) return rc;
     if (N == 0 || C == 0 || HW == 0) return SSTEM_OK;
     if (!x || !y || !save_mean || !save_invstd) return fail(SSTEM_ERR_NULL_POINTER, "batchnorm: null tensor pointer");
     if (partials && n_partials <= 0) return fail(SSTEM_ERR_BAD_SHAPE, "batchnorm: partials without a count");
@@ -1074,8 +1099,7 @@ int sstem_batchnorm_train_forward_amax_f32(const float* x, const float* weight, 
                                                   workspace, (int)N, (int)C, HW, momentum, eps, act, slope,
                                                   static_cast<hipStream_t>(stream), partials, n_partials,
                                                   reinterpret_cast<long long*>(num_batches_tracked), y_amax);
-    if (e != hipSuccess) return hip_fail("batchnorm forward launch", e);
-    return SSTEM_OK;
+    return launched("batchnorm forward launch", e);
 }
 
 int sstem_batchnorm_train_backward_f32(const float* dy, const float* x, const float* weight, const float* bias,
@@ -1105,15 +1129,14 @@ int sstem_batchnorm_train_backward_amax_f32(const float* dy, const float* x, con
                                             int64_t N, int64_t C, int64_t HW, int act, float slope, int accumulate, void* stream)
 {
     if (!bn_sizes_ok(N, C, HW)) return fail(SSTEM_ERR_BAD_SHAPE, "batchnorm: bad shape");
-    if (act < 0 || act > 2) return fail(SSTEM_ERR_UNSUPPORTED, "batchnorm: unknown activation id");
+    if (int rc = check_act("batchnorm", act)) return rc;
     if (N == 0 || C == 0 || HW == 0) return SSTEM_OK;
     if (!dy || !x || !dx || !save_mean || !save_invstd) return fail(SSTEM_ERR_NULL_POINTER, "batchnorm: null tensor pointer");
     if (!workspace || workspace_floats < sstem::bn_workspace_floats(N, C, HW))
         return fail(SSTEM_ERR_BAD_SHAPE, "batchnorm: workspace too small (see sstem_batchnorm_workspace_floats)");
     hipError_t e = sstem::launch_bn_train_backward(dy, x, weight, bias, save_mean, save_invstd, dx, dweight, dbias, workspace,
                                                    (int)N, (int)C, HW, act, slope, static_cast<hipStream_t>(stream), accumulate ? 1 : 0, dx_amax);
-    if (e != hipSuccess) return hip_fail("batchnorm backward launch", e);
-    return SSTEM_OK;
+    return launched("batchnorm backward launch", e);
 }
 
 int sstem_upsample_bilinear2x_f32(const float* input, float* output, int64_t planes, int64_t H, int64_t W, void* stream)
@@ -1125,8 +1148,7 @@ int sstem_upsample_bilinear2x_f32(const float* input, float* output, int64_t pla
     if (!input || !output) return fail(SSTEM_ERR_NULL_POINTER, "upsample: null pointer");
     if ((reinterpret_cast<uintptr_t>(output) & 15) != 0) return fail(SSTEM_ERR_UNSUPPORTED, "upsample: output must be 16-byte aligned");
     hipError_t e = sstem::launch_upsample_bilinear2x(input, output, planes, (int)H, (int)W, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("upsample launch", e);
-    return SSTEM_OK;
+    return launched("upsample launch", e);
 }
 
 int sstem_upsample_bilinear2x_backward_f32(const float* grad_output, float* grad_input, int64_t planes, int64_t H, int64_t W, void* stream)
@@ -1136,8 +1158,7 @@ int sstem_upsample_bilinear2x_backward_f32(const float* grad_output, float* grad
     if (planes == 0 || H == 0 || W == 0) return SSTEM_OK;
     if (!grad_output || !grad_input) return fail(SSTEM_ERR_NULL_POINTER, "upsample backward: null pointer");
     hipError_t e = sstem::launch_upsample_bilinear2x_backward(grad_output, grad_input, planes, (int)H, (int)W, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("upsample backward launch", e);
-    return SSTEM_OK;
+    return launched("upsample backward launch", e);
 }
 
 int sstem_pool2x2_forward_f32(const float* input, float* output, uint8_t* argmax, int64_t planes, int64_t H, int64_t W, int is_max, void* stream)
@@ -1148,8 +1169,7 @@ int sstem_pool2x2_forward_f32(const float* input, float* output, uint8_t* argmax
     if (!input || !output) return fail(SSTEM_ERR_NULL_POINTER, "pool2x2: null pointer");
     hipError_t e = sstem::launch_pool2x2_forward(input, output, is_max ? argmax : nullptr, planes, (int)H, (int)W, is_max ? 1 : 0,
                                                  static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("pool2x2 launch", e);
-    return SSTEM_OK;
+    return launched("pool2x2 launch", e);
 }
 
 int sstem_pool2x2_backward_f32(const float* grad_output, const uint8_t* argmax, float* grad_input, int64_t planes, int64_t H, int64_t W,
@@ -1162,8 +1182,7 @@ int sstem_pool2x2_backward_f32(const float* grad_output, const uint8_t* argmax, 
     if (is_max && H >= 2 && W >= 2 && !argmax) return fail(SSTEM_ERR_NULL_POINTER, "pool2x2 backward: the maximum needs its argmax bytes");
     hipError_t e = sstem::launch_pool2x2_backward(grad_output, argmax, grad_input, planes, (int)H, (int)W, is_max ? 1 : 0,
                                                   static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("pool2x2 backward launch", e);
-    return SSTEM_OK;
+    return launched("pool2x2 backward launch", e);
 }
 
 int sstem_f32_to_gray_u8(const float* pred, uint8_t* output, int64_t npix, int clamp01, void* stream)
@@ -1172,8 +1191,7 @@ int sstem_f32_to_gray_u8(const float* pred, uint8_t* output, int64_t npix, int c
     if (npix == 0) return SSTEM_OK;
     if (!pred || !output) return fail(SSTEM_ERR_NULL_POINTER, "f32->u8: null pointer");
     hipError_t e = sstem::launch_f32_to_gray_u8(pred, output, npix, clamp01 ? 1 : 0, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("f32->u8 launch", e);
-    return SSTEM_OK;
+    return launched("f32->u8 launch", e);
 }
 
 int sstem_adam_step_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
@@ -1187,8 +1205,7 @@ int sstem_adam_step_f32(float* param, const float* grad, float* exp_avg, float* 
     const double bc2 = 1.0 - pow((double)beta2, (double)step);
     hipError_t e = sstem::launch_adam_step(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay,
                                            (float)bc1, (float)sqrt(bc2), static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("adam launch", e);
-    return SSTEM_OK;
+    return launched("adam launch", e);
 }
 
 // ---- any filter length (the reference's cupy spelling: sff_scripts_interp/model/sepconv.py:8-31, SIZE_1(vertical)) -----------------
@@ -1196,30 +1213,24 @@ int sstem_sepconv_forward_taps_f32(const float* input, const float* vertical, co
                                    int64_t B, int64_t C, int64_t H, int64_t W, int taps, void* stream)
 {
     if (taps == SSTEM_SEPCONV_FILTER) return sstem_sepconv_forward_f32(input, vertical, horizontal, output, B, C, H, W, stream);
-    if (taps < 1 || taps > 1024 || B < 0 || C < 0 || H < 0 || W < 0 ||
-        (__int128)B * (C > taps ? C : taps) * (H + taps) * (W + taps) >= ((__int128)1 << 46))
-        return fail(SSTEM_ERR_BAD_SHAPE, "forward (any filter length): bad shape or filter length");
+    if (!taps_sizes_ok(B, C, H, W, taps)) return fail(SSTEM_ERR_BAD_SHAPE, "forward (any filter length): bad shape or filter length");
     if (B == 0 || C == 0 || H == 0 || W == 0) return SSTEM_OK;
     if (!input || !vertical || !horizontal || !output) return fail(SSTEM_ERR_NULL_POINTER, "forward (any filter length): null tensor pointer");
     hipError_t e = sstem::launch_fwd_direct(input, vertical, horizontal, output, B, C, H, W, taps, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("sepconv forward (any filter length) launch", e);
-    return SSTEM_OK;
+    return launched("sepconv forward (any filter length) launch", e);
 }
 
 int sstem_sepconv_backward_taps_f32(const float* grad_output, const float* input, const float* vertical, const float* horizontal,
                                     float* grad_vertical, float* grad_horizontal,
                                     int64_t B, int64_t C, int64_t H, int64_t W, int taps, void* stream)
 {
-    if (taps < 1 || taps > 1024 || B < 0 || C < 0 || H < 0 || W < 0 ||
-        (__int128)B * (C > taps ? C : taps) * (H + taps) * (W + taps) >= ((__int128)1 << 46))
-        return fail(SSTEM_ERR_BAD_SHAPE, "backward (any filter length): bad shape or filter length");
+    if (!taps_sizes_ok(B, C, H, W, taps)) return fail(SSTEM_ERR_BAD_SHAPE, "backward (any filter length): bad shape or filter length");
     if (B == 0 || C == 0 || H == 0 || W == 0) return SSTEM_OK;
     if (!grad_output || !input || !vertical || !horizontal || !grad_vertical || !grad_horizontal)
         return fail(SSTEM_ERR_NULL_POINTER, "backward (any filter length): null tensor pointer");
     hipError_t e = sstem::launch_bwd_direct(grad_output, input, vertical, horizontal, grad_vertical, grad_horizontal, B, C, H, W, taps,
                                             static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("sepconv backward (any filter length) launch", e);
-    return SSTEM_OK;
+    return launched("sepconv backward (any filter length) launch", e);
 }
 
 // ---- bf16 coefficient tensors (BASELINE config 5: "bf16 activations with fp32 sepconv accumulate") -------------------
@@ -1246,8 +1257,7 @@ int sstem_sepconv_forward_bf16coef(const float* input, const uint16_t* vertical,
     if (!input || !vertical || !horizontal || !output) return fail(SSTEM_ERR_NULL_POINTER, "forward (bf16 coefficients): null tensor pointer");
     if (!sstem::mfma_grid_ok(B, H, W)) return fail(SSTEM_ERR_UNSUPPORTED, "forward (bf16 coefficients): grid too large");
     hipError_t e = sstem::launch_fwd_bf16coef(input, vertical, horizontal, output, B, C, H, W, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("sepconv forward (bf16 coefficients) launch", e);
-    return SSTEM_OK;
+    return launched("sepconv forward (bf16 coefficients) launch", e);
 }
 
 int sstem_sepconv_backward_bf16coef(const float* grad_output, const float* input, const uint16_t* vertical, const uint16_t* horizontal,
@@ -1263,28 +1273,20 @@ int sstem_sepconv_backward_bf16coef(const float* grad_output, const float* input
     if (!sstem::mfma_grid_ok(B, H, W)) return fail(SSTEM_ERR_UNSUPPORTED, "backward (bf16 coefficients): grid too large");
     hipError_t e = sstem::launch_bwd_bf16coef(grad_output, input, vertical, horizontal, grad_vertical, grad_horizontal, B, C, H, W,
                                               static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("sepconv backward (bf16 coefficients) launch", e);
-    return SSTEM_OK;
+    return launched("sepconv backward (bf16 coefficients) launch", e);
 }
 
-int sstem_sepconv_interp_apply_gray_bf16coef_supported(int64_t B, int64_t H, int64_t W)
-{
-    return (sizes_ok(B, 3, H, W) && B > 0 && H > 0 && W > 0 && sstem::mfma_grid_ok(B, H, W) && sstem::interp_fused_gray_bf16coef_ok(H, W)) ? 1 : 0;
-}
+int sstem_sepconv_interp_apply_gray_bf16coef_supported(int64_t B, int64_t H, int64_t W) { return apply_supported(APPLY_GRAY_BF16COEF, B, H, W); }
 
 int sstem_sepconv_interp_apply_gray_bf16coef(const float* g1, const float* g2, const uint16_t* k1v, const uint16_t* k1h,
                                              const uint16_t* k2v, const uint16_t* k2h, float* output,
                                              int64_t B, int64_t H, int64_t W, void* stream)
 {
-    if (!sizes_ok(B, 3, H, W)) return fail(SSTEM_ERR_BAD_SHAPE, "gray interp apply (bf16 coefficients): negative or oversized shape");
-    if (B == 0 || H == 0 || W == 0) return SSTEM_OK;
-    if (!g1 || !g2 || !k1v || !k1h || !k2v || !k2h || !output)
-        return fail(SSTEM_ERR_NULL_POINTER, "gray interp apply (bf16 coefficients): null tensor pointer");
-    if (!sstem_sepconv_interp_apply_gray_bf16coef_supported(B, H, W))
-        return fail(SSTEM_ERR_UNSUPPORTED, "gray interp apply (bf16 coefficients): grid too large or 51*H*W*4 bytes per image not below 4 GiB");
-    hipError_t e = sstem::launch_interp_fused_gray_bf16coef(g1, g2, k1v, k1h, k2v, k2h, output, B, H, W, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("gray interp apply (bf16 coefficients) launch", e);
-    return SSTEM_OK;
+    const char* range = "grid too large or 51*H*W*4 bytes per image not below 4 GiB";      // one refusal for both range rules
+    return interp_apply("gray interp apply (bf16 coefficients)", APPLY_GRAY_BF16COEF, !g1 || !g2 || !k1v || !k1h || !k2v || !k2h || !output,
+                        B, H, W, range, range, [&] {
+        return sstem::launch_interp_fused_gray_bf16coef(g1, g2, k1v, k1h, k2v, k2h, output, B, H, W, static_cast<hipStream_t>(stream));
+    });
 }
 
 // ---- input gradient (the library's addition: the reference's launcher leaves gradInput untouched, kernel.cu:152-206) ---------------
@@ -1297,9 +1299,7 @@ int64_t sstem_sepconv_backward_input_bytes(int64_t B, int64_t C, int64_t H, int6
 static int backward_input(const char* what, const float* grad_output, const float* vertical, const float* horizontal, float* grad_input,
                           int64_t B, int64_t C, int64_t H, int64_t W, int taps, bool bf16, void* stream, int algo)
 {
-    if (taps < 1 || taps > 1024 || B < 0 || C < 0 || H < 0 || W < 0 || !sizes_ok(B, C, H, W) ||
-        (__int128)B * (C > taps ? C : taps) * (H + taps) * (W + taps) >= ((__int128)1 << 46))
-        return fail(SSTEM_ERR_BAD_SHAPE, "%s: bad shape or filter length", what);
+    if (!sizes_ok(B, C, H, W) || !taps_sizes_ok(B, C, H, W, taps)) return fail(SSTEM_ERR_BAD_SHAPE, "%s: bad shape or filter length", what);
     if (algo != SSTEM_SEPCONV_AUTO && algo != SSTEM_SEPCONV_DIRECT && algo != SSTEM_SEPCONV_MFMA)
         return fail(SSTEM_ERR_UNSUPPORTED, "%s: unknown algorithm id", what);
     if (B == 0 || C == 0) return SSTEM_OK;
@@ -1309,9 +1309,7 @@ static int backward_input(const char* what, const float* grad_output, const floa
     if (H == 0 || W == 0) {   // no source pixel: every grad_input element is an empty sum
         const size_t bytes = (size_t)B * C * (H + taps - 1) * (W + taps - 1) * sizeof(float);
         if (bytes == 0) return SSTEM_OK;
-        hipError_t e = hipMemsetAsync(grad_input, 0, bytes, s);
-        if (e != hipSuccess) return hip_fail("sepconv input gradient memset", e);
-        return SSTEM_OK;
+        return launched("sepconv input gradient memset", hipMemsetAsync(grad_input, 0, bytes, s));
     }
     const bool tiled_can = !bf16 && taps == SSTEM_SEPCONV_FILTER && sstem::gradinput_tiled_ok(B, C, H, W);
     if (algo == SSTEM_SEPCONV_AUTO) algo = tiled_can ? SSTEM_SEPCONV_MFMA : SSTEM_SEPCONV_DIRECT;
@@ -1322,8 +1320,7 @@ static int backward_input(const char* what, const float* grad_output, const floa
     } else {
         e = sstem::launch_gradinput_direct(grad_output, vertical, horizontal, grad_input, B, C, H, W, taps, bf16, s);
     }
-    if (e != hipSuccess) return hip_fail("sepconv input gradient launch", e);
-    return SSTEM_OK;
+    return launched("sepconv input gradient launch", e);
 }
 
 int sstem_sepconv_backward_input_f32_algo(const float* grad_output, const float* vertical, const float* horizontal, float* grad_input,
@@ -1362,8 +1359,7 @@ int sstem_l1_mean_forward_grad_f32(const float* pred, const float* target, int64
     if (n < 1 || n > ((int64_t)1 << 40)) return fail(SSTEM_ERR_BAD_SHAPE, "l1: bad size");
     if (!pred || !target || !loss || !grad || !workspace) return fail(SSTEM_ERR_NULL_POINTER, "l1: null pointer");
     hipError_t e = sstem::launch_l1_mean_fwd_grad(pred, target, n, loss, grad, workspace, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail("l1 launch", e);
-    return SSTEM_OK;
+    return launched("l1 launch", e);
 }
 
 }  // extern "C"

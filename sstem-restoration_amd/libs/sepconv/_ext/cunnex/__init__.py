@@ -26,7 +26,7 @@ __all__ = [
     "load_library",
 ]
 
-from sstem_native import C_ABI, library_path, load_library  # noqa: F401  (one loader for the whole C-ABI)
+from sstem_native import C_ABI, check, library_path, load_library  # noqa: F401  (one loader for the whole C-ABI)
 
 ALGO_AUTO, ALGO_DIRECT, ALGO_MFMA = 0, 1, 2
 _forced_algo = ALGO_AUTO
@@ -38,12 +38,6 @@ def set_algorithm(algo):
     if algo not in (ALGO_AUTO, ALGO_DIRECT, ALGO_MFMA):
         raise ValueError("unknown sepconv algorithm id %r" % (algo,))
     _forced_algo = algo
-
-
-def _raise_status(lib, rc, what):
-    detail = lib.sstem_last_error().decode("utf-8", "replace")
-    name = lib.sstem_status_string(rc).decode("utf-8", "replace")
-    raise RuntimeError("%s failed: %s (%d)%s" % (what, name, rc, (": " + detail) if detail else ""))
 
 
 def _dev_tensor(t, name, coef=False):
@@ -68,91 +62,68 @@ def _same_device(tensors):
     return dev
 
 
-def SeparableConvolution_cuda_forward(input, vertical, horizontal, output):
-    lib = load_library()
-    ts = [_dev_tensor(input, "input"), _dev_tensor(vertical, "vertical", coef=True),
-          _dev_tensor(horizontal, "horizontal", coef=True), _dev_tensor(output, "output")]
+def _checked(named, vertical, horizontal, then=()):
+    """The prologue of the three entry points: every (tensor, name) of `named` is a usable device tensor, the two coefficient
+    tensors have one dtype, then the tensors of `then`, and all live on one device.  -> (bfloat16 coefficients?, the device)"""
+    ts = [_dev_tensor(t, name, coef=name in ("vertical", "horizontal")) for t, name in named]
     if vertical.dtype != horizontal.dtype:
         raise TypeError("vertical and horizontal must have one dtype (%s vs %s)" % (vertical.dtype, horizontal.dtype))
-    bf16 = vertical.dtype == torch.bfloat16
-    dev = _same_device(ts)
+    ts += [_dev_tensor(t, name) for t, name in then]
+    return vertical.dtype == torch.bfloat16, _same_device(ts)
+
+
+def _launch(dev, entry, args, after_stream=(), what=None):
+    """entry(*args, the current stream of dev, *after_stream); a status other than 0 raises under the entry's name, or `what`."""
+    with torch.cuda.device(dev):
+        rc = getattr(load_library(), entry)(*args, torch.cuda.current_stream().cuda_stream, *after_stream)
+    check(rc, what or entry)
+    return 1
+
+
+def SeparableConvolution_cuda_forward(input, vertical, horizontal, output):
+    load_library()
+    bf16, dev = _checked([(input, "input"), (vertical, "vertical"), (horizontal, "horizontal"), (output, "output")], vertical, horizontal)
     B, C, H, W = output.shape
     if tuple(input.shape) != (B, C, H + 50, W + 50) or tuple(vertical.shape) != (B, 51, H, W) \
             or tuple(horizontal.shape) != (B, 51, H, W):
         raise RuntimeError("sepconv forward: inconsistent shapes in=%s v=%s h=%s out=%s" % (
             tuple(input.shape), tuple(vertical.shape), tuple(horizontal.shape), tuple(output.shape)))
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        if bf16:
-            rc = lib.sstem_sepconv_forward_bf16coef(input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), output.data_ptr(),
-                                                    B, C, H, W, stream)
-        else:
-            rc = lib.sstem_sepconv_forward_f32_algo(
-                input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), output.data_ptr(),
-                B, C, H, W, stream, _forced_algo)
-    if rc != 0:
-        _raise_status(lib, rc, "sstem_sepconv_forward_bf16coef" if bf16 else "sstem_sepconv_forward_f32")
-    return 1
+    args = [input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), output.data_ptr(), B, C, H, W]
+    if bf16:
+        return _launch(dev, "sstem_sepconv_forward_bf16coef", args)
+    return _launch(dev, "sstem_sepconv_forward_f32_algo", args, (_forced_algo,), what="sstem_sepconv_forward_f32")
 
 
 def SeparableConvolution_cuda_backward(gradLoss, input, vertical, horizontal,
                                        gradInput, gradVertical, gradHorizontal):
-    lib = load_library()
-    ts = [_dev_tensor(gradLoss, "gradLoss"), _dev_tensor(input, "input"),
-          _dev_tensor(vertical, "vertical", coef=True), _dev_tensor(horizontal, "horizontal", coef=True),
-          _dev_tensor(gradVertical, "gradVertical"), _dev_tensor(gradHorizontal, "gradHorizontal")]      # gradients: always float32
-    if vertical.dtype != horizontal.dtype:
-        raise TypeError("vertical and horizontal must have one dtype (%s vs %s)" % (vertical.dtype, horizontal.dtype))
-    bf16 = vertical.dtype == torch.bfloat16
-    if gradInput is not None:
-        ts.append(_dev_tensor(gradInput, "gradInput"))
-    dev = _same_device(ts)
+    load_library()
+    bf16, dev = _checked([(gradLoss, "gradLoss"), (input, "input"), (vertical, "vertical"), (horizontal, "horizontal"),
+                          (gradVertical, "gradVertical"), (gradHorizontal, "gradHorizontal")],      # gradients: always float32
+                         vertical, horizontal, then=[(gradInput, "gradInput")] if gradInput is not None else [])
     B, C, H, W = gradLoss.shape
     if tuple(input.shape) != (B, C, H + 50, W + 50) or tuple(vertical.shape) != (B, 51, H, W) \
             or tuple(horizontal.shape) != (B, 51, H, W) \
             or gradVertical.shape != vertical.shape or gradHorizontal.shape != horizontal.shape:
         raise RuntimeError("sepconv backward: inconsistent shapes")
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        if bf16:
-            rc = lib.sstem_sepconv_backward_bf16coef(
-                gradLoss.data_ptr(), input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(),
-                gradInput.data_ptr() if gradInput is not None else None,
-                gradVertical.data_ptr(), gradHorizontal.data_ptr(), B, C, H, W, stream)
-        else:
-            rc = lib.sstem_sepconv_backward_f32_algo(
-                gradLoss.data_ptr(), input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(),
-                gradInput.data_ptr() if gradInput is not None else None,
-                gradVertical.data_ptr(), gradHorizontal.data_ptr(),
-                B, C, H, W, stream, _forced_algo)
-    if rc != 0:
-        _raise_status(lib, rc, "sstem_sepconv_backward_bf16coef" if bf16 else "sstem_sepconv_backward_f32")
-    return 1
+    args = [gradLoss.data_ptr(), input.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(),
+            gradInput.data_ptr() if gradInput is not None else None, gradVertical.data_ptr(), gradHorizontal.data_ptr(), B, C, H, W]
+    if bf16:
+        return _launch(dev, "sstem_sepconv_backward_bf16coef", args)
+    return _launch(dev, "sstem_sepconv_backward_f32_algo", args, (_forced_algo,), what="sstem_sepconv_backward_f32")
 
 
 def SeparableConvolution_cuda_backward_input(gradLoss, vertical, horizontal, gradInput):
     """gradInput[B,C,H+50,W+50] = the input gradient of the op -- this package's addition: the reference's backward never writes its
     gradInput (kernel.cu:152-206).  Every element is written; ``set_algorithm`` is honoured (fp32 coefficients)."""
-    lib = load_library()
-    ts = [_dev_tensor(gradLoss, "gradLoss"), _dev_tensor(vertical, "vertical", coef=True),
-          _dev_tensor(horizontal, "horizontal", coef=True), _dev_tensor(gradInput, "gradInput")]
-    if vertical.dtype != horizontal.dtype:
-        raise TypeError("vertical and horizontal must have one dtype (%s vs %s)" % (vertical.dtype, horizontal.dtype))
-    bf16 = vertical.dtype == torch.bfloat16
-    dev = _same_device(ts)
+    load_library()
+    bf16, dev = _checked([(gradLoss, "gradLoss"), (vertical, "vertical"), (horizontal, "horizontal"), (gradInput, "gradInput")],
+                         vertical, horizontal)
     B, C, H, W = gradLoss.shape
     if tuple(gradInput.shape) != (B, C, H + 50, W + 50) or tuple(vertical.shape) != (B, 51, H, W) \
             or tuple(horizontal.shape) != (B, 51, H, W):
         raise RuntimeError("sepconv backward input: inconsistent shapes g=%s v=%s h=%s gradInput=%s" % (
             tuple(gradLoss.shape), tuple(vertical.shape), tuple(horizontal.shape), tuple(gradInput.shape)))
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        if bf16:
-            rc = lib.sstem_sepconv_backward_input_bf16coef(gradLoss.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(),
-                                                           gradInput.data_ptr(), B, C, H, W, stream)
-        else:
-            rc = lib.sstem_sepconv_backward_input_f32_algo(gradLoss.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(),
-                                                           gradInput.data_ptr(), B, C, H, W, stream, _forced_algo)
-    if rc != 0:
-        _raise_status(lib, rc, "sstem_sepconv_backward_input_bf16coef" if bf16 else "sstem_sepconv_backward_input_f32")
-    return 1
+    args = [gradLoss.data_ptr(), vertical.data_ptr(), horizontal.data_ptr(), gradInput.data_ptr(), B, C, H, W]
+    if bf16:
+        return _launch(dev, "sstem_sepconv_backward_input_bf16coef", args)
+    return _launch(dev, "sstem_sepconv_backward_input_f32_algo", args, (_forced_algo,), what="sstem_sepconv_backward_input_f32")

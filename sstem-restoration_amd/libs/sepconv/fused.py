@@ -11,25 +11,38 @@ import torch
 import sstem_native
 
 
-def interp_apply(i1, i2, k1v, k1h, k2v, k2h):
-    ts = [i1, i2, k1v, k1h, k2v, k2h]
-    for t in ts:
+def _apply(name, entry, ts, planes, coef_dtype=torch.float32, layout="nchw", copy=True, u8=False):
+    """The five wrappers below.  ts: two frames of `planes` channels and four coefficient tensors of `coef_dtype`, [B,51,H,W]
+    ("nchw"), ``coef_blocked_shape`` ("blocked") or whichever of the two they have ("either").  copy: non-contiguous tensors are
+    copied, else refused.  u8: the entry also stores the uint8 image and takes the layout as a flag."""
+    if coef_dtype is torch.bfloat16:
+        needs = "float32 planes and bfloat16 coefficient tensors"
+    else:
+        needs = "float32 tensors" if copy else "contiguous float32 tensors"
+    for t, dtype in zip(ts, [torch.float32] * 2 + [coef_dtype] * 4):
         if not t.is_cuda:
-            raise NotImplementedError("interp_apply is GPU-only")
-        if t.dtype != torch.float32:
-            raise TypeError("interp_apply needs float32 tensors")
-    B, C, H, W = i1.shape
-    if C != 3 or tuple(i2.shape) != (B, 3, H, W) or any(tuple(k.shape) != (B, 51, H, W) for k in ts[2:]):
-        raise RuntimeError("interp_apply: inconsistent shapes")
-    i1, i2, k1v, k1h, k2v, k2h = (t.contiguous() for t in ts)
-    out = i1.new_empty((B, 1, H, W))
-    lib = sstem_native.load_library()
-    with torch.cuda.device(i1.device):
-        rc = lib.sstem_sepconv_interp_apply_f32(i1.data_ptr(), i2.data_ptr(), k1v.data_ptr(), k1h.data_ptr(),
-                                                k2v.data_ptr(), k2h.data_ptr(), out.data_ptr(), B, H, W,
-                                                torch.cuda.current_stream().cuda_stream)
-    sstem_native.check(rc, "sstem_sepconv_interp_apply_f32")
-    return out
+            raise NotImplementedError("%s is GPU-only" % name)
+        if t.dtype != dtype or not (copy or t.is_contiguous()):
+            raise TypeError("%s needs %s" % (name, needs))
+    B, C, H, W = ts[0].shape
+    blocked = layout == "blocked" or (layout == "either" and ts[2].dim() == 5)
+    want = coef_blocked_shape(B, H, W) if blocked else (B, 51, H, W)
+    if C != planes or tuple(ts[1].shape) != (B, planes, H, W) or any(tuple(k.shape) != want for k in ts[2:]):
+        raise RuntimeError("%s: inconsistent shapes" % name)
+    if copy:
+        ts = [t.contiguous() for t in ts]
+    outs = [ts[0].new_empty((B, 1, H, W))]
+    if u8:
+        outs.append(torch.empty((B, H, W), dtype=torch.uint8, device=ts[0].device))
+    args = [t.data_ptr() for t in ts + outs] + [B, H, W] + ([1 if blocked else 0] if u8 else [])
+    with torch.cuda.device(ts[0].device):
+        rc = getattr(sstem_native.load_library(), entry)(*args, torch.cuda.current_stream().cuda_stream)
+    sstem_native.check(rc, entry)
+    return tuple(outs) if u8 else outs[0]
+
+
+def interp_apply(i1, i2, k1v, k1h, k2v, k2h):
+    return _apply("interp_apply", "sstem_sepconv_interp_apply_f32", [i1, i2, k1v, k1h, k2v, k2h], planes=3)
 
 
 def interp_apply_gray_supported(B, H, W):
@@ -40,24 +53,7 @@ def interp_apply_gray(g1, g2, k1v, k1h, k2v, k2h):
     """The same apply for callers that built the x3 channel replication themselves (every caller of the reference does:
     inference_singleImage.py:55-61, test_fusion.py:105-106): g1, g2 are the single planes [B,1,H,W].  Bit-identical to
     ``interp_apply`` on the replicated frames; one launch, no channel comparison (include/sstem_sepconv.h)."""
-    ts = [g1, g2, k1v, k1h, k2v, k2h]
-    for t in ts:
-        if not t.is_cuda:
-            raise NotImplementedError("interp_apply_gray is GPU-only")
-        if t.dtype != torch.float32:
-            raise TypeError("interp_apply_gray needs float32 tensors")
-    B, C, H, W = g1.shape
-    if C != 1 or tuple(g2.shape) != (B, 1, H, W) or any(tuple(k.shape) != (B, 51, H, W) for k in ts[2:]):
-        raise RuntimeError("interp_apply_gray: inconsistent shapes")
-    g1, g2, k1v, k1h, k2v, k2h = (t.contiguous() for t in ts)
-    out = g1.new_empty((B, 1, H, W))
-    lib = sstem_native.load_library()
-    with torch.cuda.device(g1.device):
-        rc = lib.sstem_sepconv_interp_apply_gray_f32(g1.data_ptr(), g2.data_ptr(), k1v.data_ptr(), k1h.data_ptr(),
-                                                     k2v.data_ptr(), k2h.data_ptr(), out.data_ptr(), B, H, W,
-                                                     torch.cuda.current_stream().cuda_stream)
-    sstem_native.check(rc, "sstem_sepconv_interp_apply_gray_f32")
-    return out
+    return _apply("interp_apply_gray", "sstem_sepconv_interp_apply_gray_f32", [g1, g2, k1v, k1h, k2v, k2h], planes=1)
 
 
 # ---- blocked coefficients (include/sstem_sepconv.h): [B, H, ceil(W/64), 51, 64] -----------------------------------------------
@@ -90,23 +86,8 @@ def coef_to_blocked(coef):
 def interp_apply_gray_blocked(g1, g2, k1v, k1h, k2v, k2h):
     """``interp_apply_gray`` on coefficient tensors in the blocked layout: bit-identical output, the coefficient streams walk
     consecutive addresses."""
-    B, C, H, W = g1.shape
-    ts = [g1, g2, k1v, k1h, k2v, k2h]
-    for t in ts:
-        if not t.is_cuda:
-            raise NotImplementedError("interp_apply_gray_blocked is GPU-only")
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise TypeError("interp_apply_gray_blocked needs contiguous float32 tensors")
-    if C != 1 or tuple(g2.shape) != (B, 1, H, W) or any(tuple(k.shape) != coef_blocked_shape(B, H, W) for k in ts[2:]):
-        raise RuntimeError("interp_apply_gray_blocked: inconsistent shapes")
-    out = g1.new_empty((B, 1, H, W))
-    lib = sstem_native.load_library()
-    with torch.cuda.device(g1.device):
-        rc = lib.sstem_sepconv_interp_apply_gray_blocked_f32(g1.data_ptr(), g2.data_ptr(), k1v.data_ptr(), k1h.data_ptr(),
-                                                             k2v.data_ptr(), k2h.data_ptr(), out.data_ptr(), B, H, W,
-                                                             torch.cuda.current_stream().cuda_stream)
-    sstem_native.check(rc, "sstem_sepconv_interp_apply_gray_blocked_f32")
-    return out
+    return _apply("interp_apply_gray_blocked", "sstem_sepconv_interp_apply_gray_blocked_f32", [g1, g2, k1v, k1h, k2v, k2h], planes=1,
+                  layout="blocked", copy=False)
 
 
 # ---- bfloat16 coefficient tensors (include/sstem_sepconv.h, ..._bf16coef) ------------------------------------------------------
@@ -118,24 +99,8 @@ def interp_apply_gray_bf16coef_supported(B, H, W):
 def interp_apply_gray_bf16coef(g1, g2, k1v, k1h, k2v, k2h):
     """``interp_apply_gray`` on bfloat16 coefficient tensors [B,51,H,W] (the kernel heads' outputs handed over in bf16: half the
     coefficient bytes); planes, sums and the result float32 -- bit for bit what ``interp_apply_gray`` returns on ``k.float()``."""
-    ts = [g1, g2, k1v, k1h, k2v, k2h]
-    for t in ts:
-        if not t.is_cuda:
-            raise NotImplementedError("interp_apply_gray_bf16coef is GPU-only")
-    if any(t.dtype != torch.float32 for t in ts[:2]) or any(t.dtype != torch.bfloat16 for t in ts[2:]):
-        raise TypeError("interp_apply_gray_bf16coef needs float32 planes and bfloat16 coefficient tensors")
-    B, C, H, W = g1.shape
-    if C != 1 or tuple(g2.shape) != (B, 1, H, W) or any(tuple(k.shape) != (B, 51, H, W) for k in ts[2:]):
-        raise RuntimeError("interp_apply_gray_bf16coef: inconsistent shapes")
-    g1, g2, k1v, k1h, k2v, k2h = (t.contiguous() for t in ts)
-    out = g1.new_empty((B, 1, H, W))
-    lib = sstem_native.load_library()
-    with torch.cuda.device(g1.device):
-        rc = lib.sstem_sepconv_interp_apply_gray_bf16coef(g1.data_ptr(), g2.data_ptr(), k1v.data_ptr(), k1h.data_ptr(),
-                                                          k2v.data_ptr(), k2h.data_ptr(), out.data_ptr(), B, H, W,
-                                                          torch.cuda.current_stream().cuda_stream)
-    sstem_native.check(rc, "sstem_sepconv_interp_apply_gray_bf16coef")
-    return out
+    return _apply("interp_apply_gray_bf16coef", "sstem_sepconv_interp_apply_gray_bf16coef", [g1, g2, k1v, k1h, k2v, k2h], planes=1,
+                  coef_dtype=torch.bfloat16)
 
 
 # ---- the uint8 image stored by the apply itself (include/sstem_sepconv.h, sstem_sepconv_interp_apply_gray_u8_f32) --------------
@@ -144,23 +109,5 @@ def interp_apply_gray_u8(g1, g2, k1v, k1h, k2v, k2h):
     """``interp_apply_gray`` / ``interp_apply_gray_blocked`` (by the coefficient tensors' shape) that ALSO returns
     ``(out * 255).astype(uint8)`` -- numpy's truncation, no clamp (inference_singleImage.py:76) -- stored by the same launch:
     (out float32 [B,1,H,W], image uint8 [B,H,W])."""
-    ts = [g1, g2, k1v, k1h, k2v, k2h]
-    for t in ts:
-        if not t.is_cuda:
-            raise NotImplementedError("interp_apply_gray_u8 is GPU-only")
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise TypeError("interp_apply_gray_u8 needs contiguous float32 tensors")
-    B, C, H, W = g1.shape
-    blocked = k1v.dim() == 5
-    want = coef_blocked_shape(B, H, W) if blocked else (B, 51, H, W)
-    if C != 1 or tuple(g2.shape) != (B, 1, H, W) or any(tuple(k.shape) != want for k in ts[2:]):
-        raise RuntimeError("interp_apply_gray_u8: inconsistent shapes")
-    out = g1.new_empty((B, 1, H, W))
-    img = torch.empty((B, H, W), dtype=torch.uint8, device=g1.device)
-    lib = sstem_native.load_library()
-    with torch.cuda.device(g1.device):
-        rc = lib.sstem_sepconv_interp_apply_gray_u8_f32(g1.data_ptr(), g2.data_ptr(), k1v.data_ptr(), k1h.data_ptr(), k2v.data_ptr(),
-                                                        k2h.data_ptr(), out.data_ptr(), img.data_ptr(), B, H, W, 1 if blocked else 0,
-                                                        torch.cuda.current_stream().cuda_stream)
-    sstem_native.check(rc, "sstem_sepconv_interp_apply_gray_u8_f32")
-    return out, img
+    return _apply("interp_apply_gray_u8", "sstem_sepconv_interp_apply_gray_u8_f32", [g1, g2, k1v, k1h, k2v, k2h], planes=1,
+                  layout="either", copy=False, u8=True)
