@@ -11,11 +11,13 @@
 #include "../../include/sstem_io.h"
 #include "../../include/sstem_resize.h"
 #include "../../include/sstem_norm.h"
+#include "../../include/sstem_loss.h"
 #include "sepconv_kernels.h"
 #include "conv_kernels.h"
 #include "warp_kernels.h"
 #include "misc_kernels.h"
 #include "norm_kernels.h"
+#include "ssim_kernels.h"
 #include <math.h>
 
 namespace {
@@ -1360,6 +1362,53 @@ int sstem_l1_mean_forward_grad_f32(const float* pred, const float* target, int64
     if (!pred || !target || !loss || !grad || !workspace) return fail(SSTEM_ERR_NULL_POINTER, "l1: null pointer");
     hipError_t e = sstem::launch_l1_mean_fwd_grad(pred, target, n, loss, grad, workspace, static_cast<hipStream_t>(stream));
     return launched("l1 launch", e);
+}
+
+// ---- MS-SSIM criterion (include/sstem_loss.h): both entries make the same checks, in this order, before any HIP call ----------------
+static int ms_ssim_checked(const char* what, bool any_null, int64_t B, int64_t H, int64_t W, int levels, float max_val, const float* workspace,
+                           sstem::SsimPlan* plan, bool* empty)
+{
+    *empty = false;
+    if (B < 0 || H < 0 || W < 0) return fail(SSTEM_ERR_BAD_SHAPE, "%s: negative size", what);
+    if (levels < 1 || levels > sstem::SSIM_MAX_LEVELS) return fail(SSTEM_ERR_UNSUPPORTED, "%s: levels must be 1..5", what);
+    if (!(max_val > 0.f) || isinf(max_val)) return fail(SSTEM_ERR_UNSUPPORTED, "%s: max_val must be positive and finite", what);
+    if (B == 0) { *empty = true; return SSTEM_OK; }
+    if (any_null) return fail(SSTEM_ERR_NULL_POINTER, "%s: null pointer", what);
+    if ((H < W ? H : W) < ((int64_t)1 << levels))
+        return fail(SSTEM_ERR_BAD_SHAPE, "%s: min(H, W) must be at least 2^levels (every level is pooled 2 x 2 once more)", what);
+    if (!sstem::ms_ssim_plan(B, H, W, levels, plan))
+        return fail(SSTEM_ERR_UNSUPPORTED, "%s: sizes past the index range (H, W <= 32768 and at most 2^24 tiles of 32 x 32)", what);
+    if (reinterpret_cast<uintptr_t>(workspace) & 7) return fail(SSTEM_ERR_UNSUPPORTED, "%s: the workspace must be 8-byte aligned", what);
+    return SSTEM_OK;
+}
+
+int64_t sstem_ms_ssim_workspace_floats(int64_t B, int64_t H, int64_t W, int levels)
+{
+    sstem::SsimPlan plan;
+    if (levels < 1 || levels > sstem::SSIM_MAX_LEVELS || B < 0 || (H < W ? H : W) < ((int64_t)1 << levels)) return 0;
+    return sstem::ms_ssim_plan(B, H, W, levels, &plan) ? plan.total_floats : 0;
+}
+
+int sstem_ms_ssim_forward_f32(const float* img1, const float* img2, int64_t B, int64_t H, int64_t W, int levels, float max_val, float* value,
+                              float* terms, float* workspace, void* stream)
+{
+    sstem::SsimPlan plan;
+    bool empty;
+    const int rc = ms_ssim_checked("ms_ssim forward", !img1 || !img2 || !value || !workspace, B, H, W, levels, max_val, workspace, &plan, &empty);
+    if (rc != SSTEM_OK || empty) return rc;
+    hipError_t e = sstem::launch_ms_ssim_forward(img1, img2, B, plan, max_val, value, terms, workspace, static_cast<hipStream_t>(stream));
+    return launched("ms_ssim forward launch", e);
+}
+
+int sstem_ms_ssim_backward_f32(const float* img1, const float* img2, int64_t B, int64_t H, int64_t W, int levels, float max_val,
+                               const float* grad_value, float* grad_img1, float* workspace, void* stream)
+{
+    sstem::SsimPlan plan;
+    bool empty;
+    const int rc = ms_ssim_checked("ms_ssim backward", !img1 || !img2 || !grad_img1 || !workspace, B, H, W, levels, max_val, workspace, &plan, &empty);
+    if (rc != SSTEM_OK || empty) return rc;
+    hipError_t e = sstem::launch_ms_ssim_backward(img1, img2, B, plan, max_val, grad_value, grad_img1, workspace, static_cast<hipStream_t>(stream));
+    return launched("ms_ssim backward launch", e);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 """Single loader of ``csrc/libsstem_hip.so`` and the ctypes prototypes of its whole C-ABI
-(``include/sstem_sepconv.h``, ``include/sstem_conv.h``, ``include/sstem_warp.h``, ``include/sstem_resize.h``, ``include/sstem_norm.h``, ``include/sstem_io.h``).  No fallback: a missing library raises."""
+(``include/sstem_sepconv.h``, ``include/sstem_conv.h``, ``include/sstem_warp.h``, ``include/sstem_resize.h``, ``include/sstem_norm.h``, ``include/sstem_io.h``, ``include/sstem_loss.h``).  No fallback: a missing library raises."""
 import ctypes
 import os
 
@@ -112,6 +112,10 @@ C_ABI = {
     "sstem_adam_step_f32": (_int, [_p] * 4 + [_i64] + [_f] * 5 + [_i64, _p]),
     "sstem_l1_workspace_floats": (_i64, []),
     "sstem_l1_mean_forward_grad_f32": (_int, [_p, _p, _i64, _p, _p, _p, _p]),
+    # include/sstem_loss.h
+    "sstem_ms_ssim_workspace_floats": (_i64, [_i64] * 3 + [_int]),
+    "sstem_ms_ssim_forward_f32": (_int, [_p, _p] + [_i64] * 3 + [_int, _f] + [_p] * 4),
+    "sstem_ms_ssim_backward_f32": (_int, [_p, _p] + [_i64] * 3 + [_int, _f] + [_p] * 4),
 }
 
 

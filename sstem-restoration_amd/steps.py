@@ -23,6 +23,7 @@ import train_utils
 
 _l1 = torch.nn.functional.l1_loss
 _NATIVE_L1 = os.environ.get("SSTEM_NATIVE_L1", "1") != "0"
+_NATIVE_SSIM = os.environ.get("SSTEM_NATIVE_SSIM", "1") != "0"
 
 
 def _local_batch(global_batch):
@@ -117,8 +118,15 @@ class FusionStep(_TrainStep):
     UNET_FWD_FLOP_PER_SAMPLE = 279.6e9 / 16
     FLOW_FWD_FLOP_PER_SAMPLE = 855.2e9 / 16
 
-    def __init__(self, device, global_batch=16, size=256, lr=1e-4, seed=555, graph=False, flow=None, net=None, prefetch_flow=False):
-        """flow / net: prebuilt modules (e.g. the pretrained flow predictor a training script loads, main_fusion.py:176-189) instead of
+    def __init__(self, device, global_batch=16, size=256, lr=1e-4, seed=555, graph=False, flow=None, net=None, prefetch_flow=False,
+                 loss="l1"):
+        """loss: the criterion, cfg.TRAIN.loss of the reference (main_fusion.py:194-211).  "l1" (the default) is nn.L1Loss; "ssim" is
+        MS_SSIM(max_val=1) (train_utils.MSSSIMLoss: value and gradient from native launches; SSTEM_NATIVE_SSIM=0 selects the plain-torch
+        formulation loss.loss_ssim.ms_ssim_torch for A/B runs).  With "ssim" the step DESCENDS the value itself, as main_fusion.py:252-254
+        does (loss = criterion(pred, target); loss.backward()): the reference minimises the similarity, and so does this step -- a
+        caller who wants 1 - MS-SSIM negates the gradient.  Any other name raises AttributeError('No this loss function!'), like :211.
+
+        flow / net: prebuilt modules (e.g. the pretrained flow predictor a training script loads, main_fusion.py:176-189) instead of
         the seeded random ones; they are moved to `device`, put in eval / train mode and broadcast from rank 0 like those.  Weights
         loaded into ``self.flow`` AFTER construction are picked up too: a captured graph notices and captures again (its warm-up runs
         leave the batch buffers and the trained net's BatchNorm statistics as they found them).  With ``prefetch_flow`` the flow of
@@ -130,6 +138,8 @@ class FusionStep(_TrainStep):
         weights follow the same trajectory bit for bit (tests/test_steps_gpu.py); what changes is that the two chains, each a string
         of small launches at 2 samples per GPU, share the chip.  Protocol: ``prime(x, target)`` sets the first batch of a run (the constructor primes with its synthetic one),
         ``load_next(x, target)`` hands over the batch AFTER the one ``step()`` is about to train on."""
+        if loss not in ("l1", "ssim"):
+            raise AttributeError('No this loss function!')
         from model.model_fusionnet import FusionNet
         from model.model_unet import UNet
         from utils.image_warp_torch import SpatialTransformation
@@ -150,6 +160,13 @@ class FusionStep(_TrainStep):
         self.warp = SpatialTransformation(use_gpu=True)
         self.loss = None
         self._l1 = train_utils.L1MeanLoss(device)
+        self.loss_name = loss
+        self.criterion = self._l1
+        if loss == "ssim":
+            from loss.loss_ssim import ms_ssim_torch
+            self._native_ssim = _NATIVE_SSIM
+            self.criterion = train_utils.MSSSIMLoss(device, max_val=1.0) if _NATIVE_SSIM else ms_ssim_torch
+            self._loss_backward = self._ssim_backward
         self.prefetch_flow = bool(prefetch_flow)
         if self.prefetch_flow:
             self.x_next, self.x3_next = self.x.clone(), self.x3.clone()
@@ -158,6 +175,15 @@ class FusionStep(_TrainStep):
             self._flow_stream = torch.cuda.Stream(device)
             self._flow_and_warp(self.x, self.x3, self.inp)            # the first batch: nothing to overlap it with
         self._finish_init(graph)
+
+    def _ssim_backward(self, pred, target):
+        """loss="ssim": the MS-SSIM value and the start of the backward pass at the network's output (see __init__ on the sign)."""
+        if self._native_ssim:
+            self.loss, g = self.criterion(pred, target)
+            pred.backward(g)
+        else:
+            self.loss = self.criterion(pred, target, max_val=1.0)
+            self.loss.backward()
 
     def _graph_preserve(self):
         # prefetch_flow: every pass ends with "the next batch becomes the current one" -- three warm-up passes would drop the primed

@@ -122,6 +122,30 @@ class L1MeanLoss:
         return loss, grad.view(pred.shape)
 
 
+class MSSSIMLoss:
+    """``value, grad = MSSSIMLoss(device, max_val=1.0, levels=5)(pred, target)``: the reference's ``MS_SSIM(max_val)(pred, target)``
+    (sff_scripts_fusion/loss/loss_ssim.py:18-72, the criterion of cfg.TRAIN.loss = 'ssim': main_fusion.py:198-199,252) AND
+    d value / d pred, from ``2 * levels`` native launches (include/sstem_loss.h) -- the same call shape as ``L1MeanLoss``, so a step
+    starts its backward pass at the network's output with ``pred.backward(grad)``.  ``[B,1,H,W]`` float32 GPU tensors.
+    One object per call site and per stream: it owns the launches' workspace (pyramids, partial sums, counters), which grows when a
+    larger shape arrives -- outside graph capture, so run a shape once before capturing it."""
+
+    def __init__(self, device, max_val=1.0, levels=5):
+        from loss import loss_ssim
+        self._m = loss_ssim
+        self._wsp = loss_ssim._Workspace()
+        self.device, self.max_val, self.levels = device, float(max_val), int(levels)
+
+    def __call__(self, pred, target):
+        m = self._m
+        m._check_images(pred, target)
+        p = pred.detach().contiguous()
+        t = target.detach().contiguous()
+        value, ws = m._forward(self._wsp.lib, self._wsp, p, t, self.max_val, self.levels)
+        grad = m._backward(self._wsp.lib, ws, p, t, self.max_val, self.levels, None)
+        return value, grad.view(pred.shape)
+
+
 class GraphedCallable:
     """``fn()`` -- a step body that works on persistent tensors (inputs, the flat gradient bucket, module buffers) --
     captured ONCE into a HIP graph and replayed by ``__call__``.
