@@ -12,12 +12,14 @@
 #include "../../include/sstem_resize.h"
 #include "../../include/sstem_norm.h"
 #include "../../include/sstem_loss.h"
+#include "../../include/sstem_score.h"
 #include "sepconv_kernels.h"
 #include "conv_kernels.h"
 #include "warp_kernels.h"
 #include "misc_kernels.h"
 #include "norm_kernels.h"
 #include "ssim_kernels.h"
+#include "score_kernels.h"
 #include <math.h>
 
 namespace {
@@ -201,6 +203,35 @@ int backward_weight_split(const char* what, int pieces, bool any_null, const flo
     return launched(what, sstem::launch_conv3x3_wgrad_split_mfma(input, grad_output, grad_weight, grad_bias, workspace, (int)N, (int)Cin,
                                                                  (int)H, (int)W, (int)Cout, pieces, static_cast<hipStream_t>(stream),
                                                                  wgrad_flags(accumulate), grad_mask, input_amax, grad_amax), " launch");
+}
+
+// ---- validation scores (include/sstem_score.h): the three entries make the same checks, in this order, before any HIP call ----------
+int score_checked(const char* what, bool any_null, bool images, int64_t B, int64_t H, int64_t W, const void* result,
+                         const void* workspace, sstem::ScorePlan* plan, bool* empty)
+{
+    *empty = false;
+    if (B < 0 || H < 0 || W < 0) return fail(SSTEM_ERR_BAD_SHAPE, "%s: negative size", what);
+    if (B == 0) { *empty = true; return SSTEM_OK; }
+    if (any_null) return fail(SSTEM_ERR_NULL_POINTER, "%s: null pointer", what);
+    if (images && (H < sstem::SCORE_TAPS || W < sstem::SCORE_TAPS))
+        return fail(SSTEM_ERR_BAD_SHAPE, "%s: H and W must be at least 11 (the 'valid' map of the 11 x 11 window would be empty)", what);
+    if (!sstem::score_plan(B, H, W, plan))
+        return fail(SSTEM_ERR_UNSUPPORTED, "%s: sizes past the index range (H, W <= 32768, B <= 2^24, at most 2^24 tiles of 32 x 16)", what);
+    if ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(result)) & 7)
+        return fail(SSTEM_ERR_UNSUPPORTED, "%s: the workspace and the result must be 8-byte aligned", what);
+    return SSTEM_OK;
+}
+
+template <class T>
+int score_images(const char* what, const T* a, const T* b, int64_t B, int64_t H, int64_t W, int clamp01_a, double* scores,
+                        void* workspace, void* stream)
+{
+    sstem::ScorePlan plan;
+    bool empty;
+    const int rc = score_checked(what, !a || !b || !scores || !workspace, true, B, H, W, scores, workspace, &plan, &empty);
+    if (rc != SSTEM_OK || empty) return rc;
+    const hipError_t e = sstem::launch_score_images<T>(a, b, B, H, W, plan, clamp01_a ? 1 : 0, scores, workspace, static_cast<hipStream_t>(stream));
+    return launched(what, e, " launch");
 }
 
 }  // namespace
@@ -1409,6 +1440,37 @@ int sstem_ms_ssim_backward_f32(const float* img1, const float* img2, int64_t B, 
     if (rc != SSTEM_OK || empty) return rc;
     hipError_t e = sstem::launch_ms_ssim_backward(img1, img2, B, plan, max_val, grad_value, grad_img1, workspace, static_cast<hipStream_t>(stream));
     return launched("ms_ssim backward launch", e);
+}
+
+// ---- validation scores (include/sstem_score.h); the checks are score_checked, above --------------------------------------------
+int64_t sstem_score_workspace_bytes(int64_t B, int64_t H, int64_t W)
+{
+    sstem::ScorePlan plan;
+    return sstem::score_plan(B, H, W, &plan) ? plan.total_bytes : 0;
+}
+
+int sstem_score_images_f32(const float* a, const float* b, int64_t B, int64_t H, int64_t W, int clamp01_a, double* scores, void* workspace,
+                           void* stream)
+{
+    return score_images<float>("score images (f32)", a, b, B, H, W, clamp01_a, scores, workspace, stream);
+}
+
+int sstem_score_images_u8(const uint8_t* a, const uint8_t* b, int64_t B, int64_t H, int64_t W, int clamp01_a, double* scores, void* workspace,
+                          void* stream)
+{
+    return score_images<uint8_t>("score images (u8)", a, b, B, H, W, clamp01_a, scores, workspace, stream);
+}
+
+int sstem_flow_epe_f32(const float* flow, const float* target, int64_t B, int64_t H, int64_t W, int sparse, int mean, double* value,
+                       void* workspace, void* stream)
+{
+    sstem::ScorePlan plan;
+    bool empty;
+    const int rc = score_checked("flow epe", !flow || !target || !value || !workspace, false, B, H, W, value, workspace, &plan, &empty);
+    if (rc != SSTEM_OK || empty) return rc;
+    const hipError_t e = sstem::launch_flow_epe(flow, target, B, H, W, plan, sparse ? 1 : 0, mean ? 1 : 0, value, workspace,
+                                                static_cast<hipStream_t>(stream));
+    return launched("flow epe", e, " launch");
 }
 
 }  // extern "C"

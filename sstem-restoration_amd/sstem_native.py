@@ -1,5 +1,5 @@
 """Single loader of ``csrc/libsstem_hip.so`` and the ctypes prototypes of its whole C-ABI
-(``include/sstem_sepconv.h``, ``include/sstem_conv.h``, ``include/sstem_warp.h``, ``include/sstem_resize.h``, ``include/sstem_norm.h``, ``include/sstem_io.h``, ``include/sstem_loss.h``).  No fallback: a missing library raises."""
+(``include/sstem_sepconv.h``, ``include/sstem_conv.h``, ``include/sstem_warp.h``, ``include/sstem_resize.h``, ``include/sstem_norm.h``, ``include/sstem_io.h``, ``include/sstem_loss.h``, ``include/sstem_score.h``).  No fallback: a missing library raises."""
 import ctypes
 import os
 
@@ -116,6 +116,11 @@ C_ABI = {
     "sstem_ms_ssim_workspace_floats": (_i64, [_i64] * 3 + [_int]),
     "sstem_ms_ssim_forward_f32": (_int, [_p, _p] + [_i64] * 3 + [_int, _f] + [_p] * 4),
     "sstem_ms_ssim_backward_f32": (_int, [_p, _p] + [_i64] * 3 + [_int, _f] + [_p] * 4),
+    # include/sstem_score.h
+    "sstem_score_workspace_bytes": (_i64, [_i64] * 3),
+    "sstem_score_images_f32": (_int, [_p, _p] + [_i64] * 3 + [_int] + [_p] * 3),
+    "sstem_score_images_u8": (_int, [_p, _p] + [_i64] * 3 + [_int] + [_p] * 3),
+    "sstem_flow_epe_f32": (_int, [_p, _p] + [_i64] * 3 + [_int, _int] + [_p] * 3),
 }
 
 

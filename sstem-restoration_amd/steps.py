@@ -1,7 +1,8 @@
 """The training / inference step shapes of the reference's callers, as objects the benchmarks,
 the tests and a training script share.  Each reproduces the arithmetic of one reference loop body -- forward(s), L1,
 backward, gradient all-reduce (one flat RCCL all-reduce where the reference's nn.DataParallel reduce-adds on GPU 0),
-Adam -- on synthetic ``torch.rand`` data; data providers, logging and validation stay with the caller.
+Adam -- on synthetic ``torch.rand`` data; data providers and logging stay with the caller.  ``FusionStep.validate`` and
+``IFNetStep.validate`` are the loops' validation pass for one batch (per-image PSNR, native: utils/psnr_ssim.py).
 
 * ``FusionStep``      sff_scripts_fusion/main_fusion.py:213-259: frozen FusionNet flow -> back-warp of the SFF channels ->
                       UNet -> L1 -> backward -> all-reduce -> Adam(lr 1e-4)                       (BASELINE config 3)
@@ -112,6 +113,24 @@ class _TrainStep:
     def bucket_bytes(self):
         return [bk.nbytes for bk in self.buckets]
 
+    def _validate(self, forward, gt):
+        """The validation pass of the reference's loops (main_ms.py:250-279, main_fusion.py:309-355) for one batch: ``forward()`` with
+        the trained net in eval mode under no_grad, then per image compute_psnr of the prediction clamped to [0, 1] against ``gt`` --
+        [B] float64 on the device, from utils.psnr_ssim.score_batch(pred, gt, clamp01=True); nothing synchronises.  Eager, outside any
+        captured graph; the step's batch buffers, its gradient bucket and the net's BatchNorm running statistics are not touched.
+        Deliberate difference: the net is put back in the mode it was in (train); the reference leaves its model in eval mode after
+        the first validation, so every later training step there normalises with the running statistics.  The reference's TPAD
+        padding of the input and cropping of the prediction stay with the caller, like its data providers."""
+        from utils.psnr_ssim import score_batch
+        was_training = self.net.training
+        self.net.eval()
+        try:
+            with torch.no_grad():
+                pred = forward()
+                return score_batch(pred, gt, clamp01=True)[:, 1]
+        finally:
+            self.net.train(was_training)
+
 
 class FusionStep(_TrainStep):
     # conv flops of one sample (SURVEY 8a a11 at 256x256): trained UNet forward 279.6 G / 16, frozen FusionNet 855.2 G / 16
@@ -199,6 +218,15 @@ class FusionStep(_TrainStep):
             pred_flow = self.flow(x)
             inp[:, :3] = self.warp(x3, pred_flow.permute(0, 2, 3, 1))                 # input[:, :3] = warped_sff (:235)
 
+    def validate(self, x, gt):
+        """Per-image PSNR [B] of the eval-mode forward on x [B,6,H,W] against gt [B,1,H,W] (GPU tensors): frozen flow -> back-warp of
+        the SFF channels -> UNet, as main_fusion.py:318-327 (see ``_validate``)."""
+        def forward():
+            inp = x.clone()
+            inp[:, :3] = self.warp(x[:, :3].contiguous(), self.flow(x).permute(0, 2, 3, 1))
+            return self.net(inp)
+        return self._validate(forward, gt)
+
     def load(self, x, target):
         """The batch the next sequential ``step()`` trains on ([B,6,H,W] and [B,1,H,W], any device)."""
         if self.prefetch_flow:
@@ -264,6 +292,11 @@ class IFNetStep(_TrainStep):
 
     def flop_per_step(self):
         return 3 * self.FWD_FLOP_PER_SAMPLE * self.batch * (self.x.shape[2] / 256.0) ** 2
+
+    def validate(self, x, gt):
+        """Per-image PSNR [B] of the eval-mode forward on x [B,6,H,W] against gt [B,1,H,W] (GPU tensors), as main_ms.py:260-266
+        (see ``_validate``)."""
+        return self._validate(lambda: self.net(x), gt)
 
     def forward_backward(self):
         self.buckets[0].zero()
