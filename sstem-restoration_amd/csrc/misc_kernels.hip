@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "misc_kernels.h"
+#include "wg_reduce.h"
 
 namespace sstem {
 
@@ -582,15 +583,14 @@ hipError_t launch_adam_step(float* p, const float* g, float* m, float* v, int64_
 // main_ms.py:205, sp_scripts_train/main_fusion.py:237-249) and grad = d loss / d pred = sign(pred - target) / n (sign(0) = 0, torch's
 // convention) in one pass over the two tensors: torch spends ~10 launches on the pair (sub, abs, a two-stage mean, and in the backward
 // sign, an expanded division and a multiply) -- 40-50 us of a 3 ms step at 2 samples per GPU.  Deterministic: every workgroup leaves
-// its partial sum in ws[workgroup], the LAST one to arrive (one atomic counter) adds the partials in index order and writes the mean;
-// it also resets the counter, so the workspace (L1_WS_FLOATS floats, zero when first used) needs no launch of its own between calls
-// or between replays of a captured graph.
+// its partial sum in ws[workgroup], the last one to arrive (wg_reduce.h; the counter sits at ws[L1_MAX_WGS]) adds the partials in index
+// order, four per thread, and writes the mean; the workspace (L1_WS_FLOATS floats, zero when first used) needs no launch of its own
+// between calls or between replays of a captured graph.
 constexpr int L1_MAX_WGS = 1024;
 __global__ __launch_bounds__(256) void l1_mean_fwd_grad(const float* __restrict__ pred, const float* __restrict__ target, int64_t n,
                                                          float inv_n, float* __restrict__ loss, float* __restrict__ grad, float* __restrict__ ws)
 {
-    __shared__ float red[4];
-    __shared__ int last;
+    __shared__ float red[4][1];
     float acc = 0.f;
     const int64_t n4 = n >> 2;
     const bool vec = ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(grad)) & 15) == 0;
@@ -613,31 +613,20 @@ __global__ __launch_bounds__(256) void l1_mean_fwd_grad(const float* __restrict_
         acc += fabsf(d);
         grad[i] = d > 0.f ? inv_n : (d < 0.f ? -inv_n : (d == 0.f ? 0.f : d));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        ws[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-        __threadfence();
-        const unsigned prev = atomicAdd(reinterpret_cast<unsigned*>(ws + L1_MAX_WGS), 1u);
-        last = prev == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
-    // the last workgroup: partials in index order, four per thread, then the fixed tree above
-    float t = 0.f;
+    const float sums[1] = {acc};
+    block_sum(sums, red);
+    unsigned* counter = reinterpret_cast<unsigned*>(ws + L1_MAX_WGS);
+    if (threadIdx.x == 0) agent_store(ws + blockIdx.x, block_tree(red, 0));
+    if (!arrive_last(counter)) return;
+    // the last workgroup: partials in index order, four per thread, then the fixed tree
+    float t[1] = {0.f};
     for (int i = threadIdx.x * 4; i < (int)gridDim.x; i += 1024)
-        for (int e = 0; e < 4 && i + e < (int)gridDim.x; ++e) t += __hip_atomic_load(ws + i + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o, 64);
+        for (int e = 0; e < 4 && i + e < (int)gridDim.x; ++e) t[0] += agent_load(ws + i + e);
     __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
-    __syncthreads();
+    block_sum(t, red);
     if (threadIdx.x == 0) {
-        *loss = ((red[0] + red[1]) + (red[2] + red[3])) * inv_n;
-        *reinterpret_cast<unsigned*>(ws + L1_MAX_WGS) = 0u;
+        *loss = block_tree(red, 0) * inv_n;
+        release_counter(counter);
     }
 }
 

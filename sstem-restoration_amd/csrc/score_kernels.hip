@@ -14,9 +14,8 @@
 // this, and its `h < eps * h.max()` cut zeroes nothing at sigma = 1.5 (the smallest entry is exp(-50 / 4.5) = 1.5e-5).
 // A NaN among the values makes the maximum NaN and so selects the `> 1` branch, as np.max does.
 //
-// Sums: per-workgroup double partials; the LAST workgroup of a launch to arrive (one counter per launch, reset by that workgroup;
-// agent-scope release on the add, acquire before the reads -- ms_ssim_level_fwd's pattern) finishes every image, one wave per image:
-// lane l adds the image's partials l, l + 64, ... in index order, then the fixed tree.  An image's result depends on its own partials
+// Sums: per-workgroup double partials; the last workgroup of a launch to arrive (wg_reduce.h; one counter per launch) finishes every
+// image, one wave per image: lane l adds the image's partials l, l + 64, ... in index order.  An image's result depends on its own partials
 // only, so it is the same bits whatever its neighbours in the batch.  No float atomics, the same bits run to run.  The three counters
 // sit in the workspace's first 64 bytes whatever the shape and everything behind them is written before it is read, so one zeroed
 // workspace serves calls of any shapes (up to the size it was asked for) and graph replays without another fill.
@@ -25,6 +24,7 @@
 #include <stdint.h>
 
 #include "score_kernels.h"
+#include "wg_reduce.h"
 
 namespace sstem {
 
@@ -37,9 +37,6 @@ constexpr int SW = TW + HALO, SH = TH + HALO;   // staged extent, 42 x 26
 struct DTaps { double g[SCORE_TAPS]; };
 constexpr int CNT_EPE = 0, CNT_STATS = 1, CNT_MAP = 2;      // the workspace's first words
 
-#define SSTEM_AGENT_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define SSTEM_AGENT_STORE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-
 // np.max: a NaN, once met, stays
 __device__ __forceinline__ float nan_max(float m, float v) { return (v > m || v != v) ? v : m; }
 
@@ -48,13 +45,6 @@ __device__ __forceinline__ float clamp01(float v) { return v > 1.f ? 1.f : (v < 
 
 // (uint8)(x * 255.f) for x <= 1; below 0, where numpy's cast is undefined, 0
 __device__ __forceinline__ float quantise(float v) { return v > 0.f ? (float)(int)(v * 255.f) : 0.f; }
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
 
 __device__ __forceinline__ float wave_nan_max(float v)
 {
@@ -72,7 +62,6 @@ __global__ __launch_bounds__(256) void score_stats(const T* __restrict__ a, cons
                                                    double* partials)
 {
     __shared__ double red[4][4];
-    __shared__ int last;
     const int tid = threadIdx.x;
     const int64_t img = blockIdx.x / chunks;
     const int c = blockIdx.x - (int)img * chunks;
@@ -90,22 +79,17 @@ __global__ __launch_bounds__(256) void score_stats(const T* __restrict__ a, cons
         s_unit += d * d;
         s_255 += e * e;
     }
-    ma = wave_nan_max(ma); mb = wave_nan_max(mb);
-    s_unit = wave_sum(s_unit); s_255 = wave_sum(s_255);
-    if ((tid & 63) == 0) { red[tid >> 6][0] = ma; red[tid >> 6][1] = mb; red[tid >> 6][2] = s_unit; red[tid >> 6][3] = s_255; }
+    wave_slot(red, 0, (double)wave_nan_max(ma)); wave_slot(red, 1, (double)wave_nan_max(mb));
+    wave_slot(red, 2, wave_sum(s_unit)); wave_slot(red, 3, wave_sum(s_255));
     __syncthreads();
     double* mine = partials + 4 * (int64_t)blockIdx.x;
     if (tid == 0) {
-        SSTEM_AGENT_STORE(mine + 0, (double)nan_max(nan_max((float)red[0][0], (float)red[1][0]), nan_max((float)red[2][0], (float)red[3][0])));
-        SSTEM_AGENT_STORE(mine + 1, (double)nan_max(nan_max((float)red[0][1], (float)red[1][1]), nan_max((float)red[2][1], (float)red[3][1])));
-        SSTEM_AGENT_STORE(mine + 2, (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]));
-        SSTEM_AGENT_STORE(mine + 3, (red[0][3] + red[1][3]) + (red[2][3] + red[3][3]));
-        const unsigned prev = __hip_atomic_fetch_add(counters + CNT_STATS, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        last = prev == gridDim.x - 1;
+        agent_store(mine + 0, (double)nan_max(nan_max((float)red[0][0], (float)red[1][0]), nan_max((float)red[2][0], (float)red[3][0])));
+        agent_store(mine + 1, (double)nan_max(nan_max((float)red[0][1], (float)red[1][1]), nan_max((float)red[2][1], (float)red[3][1])));
+        agent_store(mine + 2, block_tree(red, 2));
+        agent_store(mine + 3, block_tree(red, 3));
     }
-    __syncthreads();
-    if (!last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (!arrive_last(counters + CNT_STATS)) return;
 
     // the launch's last workgroup: one wave per image, lane l takes the image's partial l (chunks <= 64), then the fixed tree
     const int lane = tid & 63;
@@ -114,10 +98,10 @@ __global__ __launch_bounds__(256) void score_stats(const T* __restrict__ a, cons
         float xa = -INFINITY, xb = -INFINITY;
         double t_unit = 0.0, t_255 = 0.0;
         if (lane < chunks) {
-            xa = (float)SSTEM_AGENT_LOAD(first + 4 * lane);
-            xb = (float)SSTEM_AGENT_LOAD(first + 4 * lane + 1);
-            t_unit = SSTEM_AGENT_LOAD(first + 4 * lane + 2);
-            t_255 = SSTEM_AGENT_LOAD(first + 4 * lane + 3);
+            xa = (float)agent_load(first + 4 * lane);
+            xb = (float)agent_load(first + 4 * lane + 1);
+            t_unit = agent_load(first + 4 * lane + 2);
+            t_255 = agent_load(first + 4 * lane + 3);
         }
         xa = wave_nan_max(xa); xb = wave_nan_max(xb);
         t_unit = wave_sum(t_unit); t_255 = wave_sum(t_255);
@@ -129,7 +113,7 @@ __global__ __launch_bounds__(256) void score_stats(const T* __restrict__ a, cons
             unit_range[i] = unit;
         }
     }
-    if (tid == 0) SSTEM_AGENT_STORE(counters + CNT_STATS, 0u);
+    if (tid == 0) release_counter(counters + CNT_STATS);
 }
 
 // Launch 2.  Workgroup = one 32 x 16 tile of one image's map; map point (oy, ox) reads image rows oy .. oy + 10, columns ox .. ox + 10.
@@ -141,8 +125,7 @@ __global__ __launch_bounds__(256) void score_ssim_map(const T* __restrict__ a, c
 {
     __shared__ float sa[SH * SW], sb[SH * SW];
     __shared__ double hb[5][SH * TW];
-    __shared__ double red[4];
-    __shared__ int last;
+    __shared__ double red[4][1];
     const int tid = threadIdx.x;
     const int64_t img = blockIdx.x / tiles;
     const int t = blockIdx.x - (int)img * tiles;
@@ -197,17 +180,10 @@ __global__ __launch_bounds__(256) void score_ssim_map(const T* __restrict__ a, c
             sum += ((2.0 * m12 + C1) * (2.0 * (v[4] - m12) + C2)) / ((m11 + m22 + C1) * ((v[2] - m11) + (v[3] - m22) + C2));
         }
     }
-    sum = wave_sum(sum);
-    if ((tid & 63) == 0) red[tid >> 6] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        SSTEM_AGENT_STORE(partials + (int64_t)blockIdx.x, (red[0] + red[1]) + (red[2] + red[3]));
-        const unsigned prev = __hip_atomic_fetch_add(counters + CNT_MAP, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        last = prev == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    const double sums[1] = {sum};
+    block_sum(sums, red);
+    if (tid == 0) agent_store(partials + (int64_t)blockIdx.x, block_tree(red, 0));
+    if (!arrive_last(counters + CNT_MAP)) return;
 
     // the launch's last workgroup: one wave per image, its tiles' partials in index order per lane, then the fixed tree
     const int lane = tid & 63;
@@ -215,11 +191,11 @@ __global__ __launch_bounds__(256) void score_ssim_map(const T* __restrict__ a, c
     for (int64_t i = tid >> 6; i < B; i += 4) {
         const double* first = partials + i * tiles;
         double total = 0.0;
-        for (int j = lane; j < tiles; j += 64) total += SSTEM_AGENT_LOAD(first + j);
+        for (int j = lane; j < tiles; j += 64) total += agent_load(first + j);
         total = wave_sum(total);
         if (lane == 0) scores[3 * i + 2] = total / count;             // np.mean divides: identical images give exactly 1
     }
-    if (tid == 0) SSTEM_AGENT_STORE(counters + CNT_MAP, 0u);
+    if (tid == 0) release_counter(counters + CNT_MAP);
 }
 
 // EPE(input_flow, target_flow, sparse, mean) for [B,2,H,W]: sqrt(dx^2 + dy^2) per pixel in float64; sparse skips the pixels whose two
@@ -230,7 +206,6 @@ __global__ __launch_bounds__(256) void flow_epe_kernel(const float* __restrict__
                                                        double* partials)
 {
     __shared__ double red[4][2];
-    __shared__ int last;
     const int tid = threadIdx.x;
     double sum = 0.0, kept = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < n; i += (int64_t)gridDim.x * 256) {
@@ -242,37 +217,25 @@ __global__ __launch_bounds__(256) void flow_epe_kernel(const float* __restrict__
         sum += sqrt(dx * dx + dy * dy);
         kept += 1.0;
     }
-    sum = wave_sum(sum); kept = wave_sum(kept);
-    if ((tid & 63) == 0) { red[tid >> 6][0] = sum; red[tid >> 6][1] = kept; }
-    __syncthreads();
+    const double sums[2] = {sum, kept};
+    block_sum(sums, red);
     if (tid == 0) {
-        SSTEM_AGENT_STORE(partials + 2 * (int64_t)blockIdx.x, (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]));
-        SSTEM_AGENT_STORE(partials + 2 * (int64_t)blockIdx.x + 1, (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]));
-        const unsigned prev = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        last = prev == gridDim.x - 1;
+        agent_store(partials + 2 * (int64_t)blockIdx.x, block_tree(red, 0));
+        agent_store(partials + 2 * (int64_t)blockIdx.x + 1, block_tree(red, 1));
     }
-    __syncthreads();
-    if (!last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (!arrive_last(counter)) return;
 
-    double t0 = 0.0, t1 = 0.0;
-    for (int i = tid; i < (int)gridDim.x; i += 256) {
-        t0 += SSTEM_AGENT_LOAD(partials + 2 * i);
-        t1 += SSTEM_AGENT_LOAD(partials + 2 * i + 1);
-    }
-    t0 = wave_sum(t0); t1 = wave_sum(t1);
-    __syncthreads();
-    if ((tid & 63) == 0) { red[tid >> 6][0] = t0; red[tid >> 6][1] = t1; }
-    __syncthreads();
+    block_total(partials, gridDim.x, red);
     if (tid != 0) return;
-    const double total = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-    const double count = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+    const double total = block_tree(red, 0), count = block_tree(red, 1);
     *value = mean ? total / count : total / batch;
-    SSTEM_AGENT_STORE(counter, 0u);
+    release_counter(counter);
 }
 
 DTaps make_taps()
 {
+    // matlab_style_gauss2D's separable factor: float64 throughout, sigma fixed at 1.5 -- not ssim_kernels.hip's make_taps, which follows
+    // torch's fp32 window with a sigma that shrinks with the window
     DTaps t;
     double sum = 0.0;
     for (int k = 0; k < SCORE_TAPS; ++k) {

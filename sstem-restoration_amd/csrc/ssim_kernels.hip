@@ -14,14 +14,14 @@
 //
 // Every window runs as 11 taps, the shorter ones padded with zero taps at the end, so the loops unroll with the taps in scalar registers;
 // the staged halo is sized for 11 and zero outside the image (a zero tap then meets a finite number).
-// Sums: a workgroup's two map sums go to the workspace as doubles, the LAST workgroup to arrive (one counter per level, reset by that
-// workgroup; agent-scope release on the add, acquire before the reads) adds them in a fixed order -- no float atomics, same bits every run,
-// nothing to clear between calls or graph replays.
+// Sums: a workgroup's two map sums go to the workspace as doubles and the level's last workgroup to arrive adds them (wg_reduce.h; one
+// counter per level).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "ssim_kernels.h"
+#include "wg_reduce.h"
 
 namespace sstem {
 
@@ -44,8 +44,20 @@ __device__ __forceinline__ float weight_of(int i)
     return i == 0 ? 0.0448f : i == 1 ? 0.2856f : i == 2 ? 0.3001f : i == 3 ? 0.2363f : 0.1333f;
 }
 
-#define SSTEM_AGENT_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define SSTEM_AGENT_STORE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+// E x E window of images x, y (h x w at `base`) from (y0, x0) into sx, sy; zero outside the image.
+template <int E>
+__device__ __forceinline__ void stage_pair(const float* __restrict__ x, const float* __restrict__ y, int64_t base, int h, int w, int y0,
+                                           int x0, float* sx, float* sy)
+{
+    for (int e = threadIdx.x; e < E * E; e += 256) {
+        const int r = e / E, c = e - r * E;
+        const int iy = y0 + r, ix = x0 + c;
+        const bool in = iy >= 0 && iy < h && ix >= 0 && ix < w;
+        const int64_t o = base + (int64_t)iy * w + ix;
+        sx[e] = in ? x[o] : 0.f;
+        sy[e] = in ? y[o] : 0.f;
+    }
+}
 
 // Forward of one level.  Workgroup = one 32 x 32 tile of one image's map (even origin, so it owns whole 2 x 2 pooling windows).
 __global__ __launch_bounds__(256) void ms_ssim_level_fwd(const float* __restrict__ x, const float* __restrict__ y, int h, int w, int oh, int ow,
@@ -57,20 +69,12 @@ __global__ __launch_bounds__(256) void ms_ssim_level_fwd(const float* __restrict
     __shared__ float sx[FE * FE], sy[FE * FE];
     __shared__ float hb[5][FE * T];
     __shared__ double red[4][2];
-    __shared__ int last;
     const int tid = threadIdx.x;
     const int b = blockIdx.x / tiles, t = blockIdx.x - b * tiles;
     const int Y0 = (t / tiles_x) * T, X0 = (t % tiles_x) * T;
     const int64_t base = (int64_t)b * h * w;
 
-    for (int e = tid; e < FE * FE; e += 256) {
-        const int r = e / FE, c = e - r * FE;
-        const int iy = Y0 - p + r, ix = X0 - p + c;
-        const bool in = iy >= 0 && iy < h && ix >= 0 && ix < w;
-        const int64_t o = base + (int64_t)iy * w + ix;
-        sx[e] = in ? x[o] : 0.f;
-        sy[e] = in ? y[o] : 0.f;
-    }
+    stage_pair<FE>(x, y, base, h, w, Y0 - p, X0 - p, sx, sy);
     __syncthreads();
 
     for (int e = tid; e < FE * T; e += 256) {
@@ -122,41 +126,26 @@ __global__ __launch_bounds__(256) void ms_ssim_level_fwd(const float* __restrict
         }
     }
 
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { sum_ssim += __shfl_down(sum_ssim, o, 64); sum_mcs += __shfl_down(sum_mcs, o, 64); }
-    if ((tid & 63) == 0) { red[tid >> 6][0] = sum_ssim; red[tid >> 6][1] = sum_mcs; }
-    __syncthreads();
+    const double sums[2] = {sum_ssim, sum_mcs};
+    block_sum(sums, red);
     unsigned* counter = reinterpret_cast<unsigned*>(ws + HDR_COUNTER) + level;
     if (tid == 0) {
-        SSTEM_AGENT_STORE(partials + 2 * (int64_t)blockIdx.x, (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]));
-        SSTEM_AGENT_STORE(partials + 2 * (int64_t)blockIdx.x + 1, (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]));
-        const unsigned prev = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        last = prev == gridDim.x - 1;
+        agent_store(partials + 2 * (int64_t)blockIdx.x, block_tree(red, 0));
+        agent_store(partials + 2 * (int64_t)blockIdx.x + 1, block_tree(red, 1));
     }
-    __syncthreads();
-    if (!last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (!arrive_last(counter)) return;
 
-    // the last workgroup of the level: partials in index order per thread, then the fixed tree
-    double t0 = 0.0, t1 = 0.0;
-    for (int64_t i = tid; i < (int64_t)gridDim.x; i += 256) {
-        t0 += SSTEM_AGENT_LOAD(partials + 2 * i);
-        t1 += SSTEM_AGENT_LOAD(partials + 2 * i + 1);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { t0 += __shfl_down(t0, o, 64); t1 += __shfl_down(t1, o, 64); }
-    __syncthreads();
-    if ((tid & 63) == 0) { red[tid >> 6][0] = t0; red[tid >> 6][1] = t1; }
-    __syncthreads();
+    // the last workgroup of the level: every thread adds partials in index order, then the fixed tree
+    block_total(partials, gridDim.x, red);
     if (tid != 0) return;
     double* dterms = reinterpret_cast<double*>(ws + HDR_DTERMS);
-    const double mean_ssim = ((red[0][0] + red[1][0]) + (red[2][0] + red[3][0])) * counts.inv[level];
-    const double mean_mcs = ((red[0][1] + red[1][1]) + (red[2][1] + red[3][1])) * counts.inv[level];
+    const double mean_ssim = block_tree(red, 0) * counts.inv[level];
+    const double mean_mcs = block_tree(red, 1) * counts.inv[level];
     dterms[2 * level] = mean_ssim; dterms[2 * level + 1] = mean_mcs;
     ws[HDR_TERMS + 2 * level] = (float)mean_ssim; ws[HDR_TERMS + 2 * level + 1] = (float)mean_mcs;
     if (terms_out) { terms_out[2 * level] = (float)mean_ssim; terms_out[2 * level + 1] = (float)mean_mcs; }
     if (level == 0) *reinterpret_cast<unsigned long long*>(ws + HDR_IMG1) = img1_addr;     // which image the first pyramid belongs to
-    SSTEM_AGENT_STORE(counter, 0u);
+    release_counter(counter);
     if (level != levels - 1) return;
     // the value and every level's coefficient; a non-positive mean gives NaN, as in the reference
     double term[SSIM_MAX_LEVELS];
@@ -164,7 +153,7 @@ __global__ __launch_bounds__(256) void ms_ssim_level_fwd(const float* __restrict
 #pragma unroll
     for (int i = 0; i < SSIM_MAX_LEVELS; ++i) {
         if (i < levels) {
-            term[i] = i == level ? (i == levels - 1 ? mean_ssim : mean_mcs) : SSTEM_AGENT_LOAD(dterms + 2 * i + 1);
+            term[i] = i == level ? (i == levels - 1 ? mean_ssim : mean_mcs) : agent_load(dterms + 2 * i + 1);
             value *= pow(term[i], (double)weight_of(i));
         }
     }
@@ -198,14 +187,7 @@ __global__ __launch_bounds__(256) void ms_ssim_level_bwd(const float* __restrict
     const float* x = swapped ? second : first;
     const float* y = swapped ? first : second;
 
-    for (int e = tid; e < BE * BE; e += 256) {
-        const int r = e / BE, c = e - r * BE;
-        const int iy = Y0 - HALO + r, ix = X0 - HALO + c;
-        const bool in = iy >= 0 && iy < h && ix >= 0 && ix < w;
-        const int64_t o = base + (int64_t)iy * w + ix;
-        sx[e] = in ? x[o] : 0.f;
-        sy[e] = in ? y[o] : 0.f;
-    }
+    stage_pair<BE>(x, y, base, h, w, Y0 - HALO, X0 - HALO, sx, sy);
     __syncthreads();
 
     const int tx = tid & 31, ty = tid >> 5;
@@ -305,7 +287,8 @@ __global__ __launch_bounds__(256) void ms_ssim_level_bwd(const float* __restrict
 
 Taps make_taps(int ws)
 {
-    // gaussian() of loss_ssim.py:8-10: double exponentials rounded to fp32, divided by their fp32 sum
+    // gaussian() of loss_ssim.py:8-10: double exponentials rounded to fp32, divided by their fp32 sum, sigma following the window --
+    // not score_kernels.hip's make_taps, which is scipy's float64 window at a fixed sigma
     Taps t;
     const double sigma = 1.5 * ws / 11;
     float f[SSIM_TAPS], sum = 0.f;
