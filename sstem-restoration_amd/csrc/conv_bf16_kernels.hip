@@ -27,12 +27,13 @@
 #include <stdlib.h>
 
 #include "conv_kernels.h"
+#include "conv_device.h"
 #include "conv_launch.h"
+#include "conv_pack.h"
 
 namespace sstem {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 
 constexpr int BKC = 16;                       // input channels per K chunk
@@ -47,15 +48,6 @@ constexpr int BIN_BYTES = 2 * BIN_HOFF;               // 11200 B per buffer
 __device__ __forceinline__ constexpr int bin_off(int row, int col, int half) { return (row * BIN_PITCH + col) * 16 + half * BIN_HOFF; }
 constexpr uint32_t OOB = 0x80000000u;         // per-lane offset of a padding lane: beyond any buffer this kernel accepts
 
-// "wave-uniform 64-bit base (SGPR pair) + one 32-bit per-lane byte offset" stores: the saddr form, no per-lane 64-bit addresses
-typedef __attribute__((address_space(1))) float gfloat_t;
-template <typename T>
-__device__ __forceinline__ void pin_uniform_ptr(T*& p) { asm volatile("" : "+s"(p)); }
-__device__ __forceinline__ void store_lane(float* ubase, uint32_t lane_byte_off, float v)
-{
-    *reinterpret_cast<gfloat_t*>(reinterpret_cast<uint64_t>(ubase) + lane_byte_off) = v;
-}
-
 typedef __attribute__((address_space(1))) __bf16 gbf16_t;
 typedef __attribute__((address_space(1))) uint8_t gbyte_bf_t;
 __device__ __forceinline__ void store_lane_b16(__bf16* ubase, uint32_t lane_byte_off, float v)
@@ -63,21 +55,18 @@ __device__ __forceinline__ void store_lane_b16(__bf16* ubase, uint32_t lane_byte
     *reinterpret_cast<gbf16_t*>(reinterpret_cast<uint64_t>(ubase) + lane_byte_off) = (__bf16)v;
 }
 
-__device__ __forceinline__ void pin_sgpr(uint32_t& v) { asm volatile("" : "+s"(v)); }
-
-__device__ __forceinline__ float act_bf(float v, int act, float slope)
-{
-    if (act == 1) return v > 0.f ? v : 0.f;
-    if (act == 2) return v > 0.f ? v : v * slope;
-    return v;
-}
-
 // W[co][ci][3][3] (or W[ci][co][3][3] read with flipped taps) -> Wp[cb][chunk][tap][CO][16] bf16, zero-padded in co and ci
-__global__ void pack_weights_3x3_bf16(const float* __restrict__ w, __bf16* __restrict__ wp, int Cin, int Cout, int CO,
-                                      int nchunks, int ncb, int transposed_flipped)
-{
-    const int64_t total = (int64_t)ncb * nchunks * 9 * CO * BKC;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+struct PackBf16 {
+    typedef __bf16 elem_t;
+    static PackSide side(int cin, int cout)
+    {
+        const int CO = conv3x3_bf16_co_block(cout);
+        const int ncb = (cout + CO - 1) / CO, nchunks = (cin + BKC - 1) / BKC;
+        return PackSide{CO, nchunks, ncb, (int64_t)ncb * nchunks * 9 * CO * BKC};
+    }
+    static __device__ __forceinline__ __bf16 slot(const float* __restrict__ w, int64_t idx, int cin, int cout, int CO, int nchunks,
+                                                  bool transposed_flipped)
+    {
         const int cl = idx % BKC;
         int64_t r = idx / BKC;
         const int col = r % CO; r /= CO;
@@ -86,66 +75,11 @@ __global__ void pack_weights_3x3_bf16(const float* __restrict__ w, __bf16* __res
         const int cb = r / nchunks;
         const int ci = chunk * BKC + cl, co = cb * CO + col;
         float v = 0.f;
-        if (ci < Cin && co < Cout)
-            v = transposed_flipped ? w[((int64_t)ci * Cout + co) * 9 + (8 - tap)] : w[((int64_t)co * Cin + ci) * 9 + tap];
-        wp[idx] = (__bf16)v;
+        if (ci < cin && co < cout)
+            v = transposed_flipped ? w[((int64_t)ci * cout + co) * 9 + (8 - tap)] : w[((int64_t)co * cin + ci) * 9 + tap];
+        return (__bf16)v;
     }
-}
-
-// Both packings of one layer's weights in one launch (see pack_weights_3x3_both in conv_kernels.hip)
-__global__ void pack_weights_3x3_bf16_both(const float* __restrict__ w, __bf16* __restrict__ wp_f, __bf16* __restrict__ wp_t, int Cin,
-                                           int Cout, int CO_f, int nchunks_f, int64_t n_fwd, int CO_t, int nchunks_t, int64_t n_t)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_fwd + n_t; i += (int64_t)gridDim.x * blockDim.x) {
-        const bool t = i >= n_fwd;
-        const int64_t idx = t ? i - n_fwd : i;
-        const int CO = t ? CO_t : CO_f, nchunks = t ? nchunks_t : nchunks_f;
-        const int cin = t ? Cout : Cin, cout = t ? Cin : Cout;
-        const int cl = idx % BKC;
-        int64_t r = idx / BKC;
-        const int col = r % CO; r /= CO;
-        const int tap = r % 9; r /= 9;
-        const int chunk = r % nchunks;
-        const int cb = r / nchunks;
-        const int ci = chunk * BKC + cl, co = cb * CO + col;
-        float v = 0.f;
-        if (ci < cin && co < cout) v = t ? w[((int64_t)ci * cout + co) * 9 + (8 - tap)] : w[((int64_t)co * cin + ci) * 9 + tap];
-        (t ? wp_t : wp_f)[idx] = (__bf16)v;
-    }
-}
-
-// Both packings of MANY layers in one launch (see pack_weights_3x3_group in conv_kernels.hip; same table layout, entries from
-// pack_group_entry_bf16)
-__global__ __launch_bounds__(256) void pack_weights_3x3_bf16_group(const int64_t* __restrict__ table, int n_entries)
-{
-    int lo = 0, hi = n_entries - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[(int64_t)mid * 16 + 13] <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const int64_t* en = table + (int64_t)lo * 16;
-    const float* w = reinterpret_cast<const float*>(en[0]);
-    __bf16* wp_f = reinterpret_cast<__bf16*>(en[1]);
-    __bf16* wp_t = reinterpret_cast<__bf16*>(en[2]);
-    const int Cin = (int)en[3], Cout = (int)en[4];
-    const int64_t n_fwd = en[8], n_t = en[12];
-    const int64_t i = ((int64_t)blockIdx.x - en[13]) * 256 + threadIdx.x;
-    if (i >= n_fwd + n_t) return;
-    const bool t = i >= n_fwd;
-    const int64_t idx = t ? i - n_fwd : i;
-    const int CO = (int)(t ? en[9] : en[5]), nchunks = (int)(t ? en[10] : en[6]);
-    const int cin = t ? Cout : Cin, cout = t ? Cin : Cout;
-    const int cl = idx % BKC;
-    int64_t r = idx / BKC;
-    const int col = r % CO; r /= CO;
-    const int tap = r % 9; r /= 9;
-    const int chunk = r % nchunks;
-    const int cb = r / nchunks;
-    const int ci = chunk * BKC + cl, co = cb * CO + col;
-    float v = 0.f;
-    if (ci < cin && co < cout) v = t ? w[((int64_t)ci * cout + co) * 9 + (8 - tap)] : w[((int64_t)co * cin + ci) * 9 + tap];
-    (t ? wp_t : wp_f)[idx] = (__bf16)v;
-}
+};
 
 // INB / OUTB (16-byte staging only): the input / output TENSOR is bf16 NCHW instead of fp32 -- what the convolutions inside one
 // Conv-ReLU-Conv block exchange under the bf16 id when no backward can follow.  Numerically free: the consumer rounds the same
@@ -287,7 +221,6 @@ __global__ __launch_bounds__(256, WPE) void conv3x3_bf16_mfma(
     }
     // (plain 16-B global loads from a uniform channel base plus the lane's offset, clamped to 0 and masked at the LDS store for
     // padding lanes: clang 19's __builtin_amdgcn_raw_buffer_load_b128 lowers to a ONE-dword load splat over the vector.)
-    typedef float f32x4v __attribute__((ext_vector_type(4)));
     const bool vok = vvoff != OOB;
     const uint32_t vsafe = vok ? vvoff : 0u;
     constexpr int ESZ = INB ? 2 : 4;                                   // bytes per input element
@@ -295,7 +228,7 @@ __global__ __launch_bounds__(256, WPE) void conv3x3_bf16_mfma(
     const uint32_t vsafeB = INB ? vsafe / 2u : vsafe;
     const char* in_n = static_cast<const char*>(in_v) + (int64_t)n * Cin * plane * ESZ;
     typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
-    f32x4v stg4[INB ? 1 : 8];
+    f32x4 stg4[INB ? 1 : 8];
     u32x2v stg2[INB ? 8 : 1];                                         // INB: 4 bf16 pixels of one channel = 8 B
     uint32_t mk4[(MASKED && !INB) ? 8 : 1];                           // MASKED: the mask bytes of the lane's four pixels, per channel
     auto issue_in_v = [&](int chunk) {
@@ -319,8 +252,8 @@ __global__ __launch_bounds__(256, WPE) void conv3x3_bf16_mfma(
                 if (chan) v = *reinterpret_cast<const u32x2v*>(pc + (int64_t)i * planeB + vsafeB);
                 stg2[i] = v;
             } else {
-                f32x4v v = {0.f, 0.f, 0.f, 0.f};
-                if (chan) v = *reinterpret_cast<const f32x4v*>(pc + (int64_t)i * planeB + vsafeB);
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                if (chan) v = *reinterpret_cast<const f32x4*>(pc + (int64_t)i * planeB + vsafeB);
                 stg4[i] = v;
             }
         }
@@ -531,7 +464,7 @@ __global__ __launch_bounds__(256, WPE) void conv3x3_bf16_mfma(
             const int y = Y0 + wr * R + rr;
             if (y < H && x < W) {
                 float v = acc[rr][q] + bs;
-                v = act_bf(v * sc + sh, act, slope);
+                v = act_apply(v * sc + sh, act, slope);
                 if constexpr (OUTB) v = (float)(__bf16)v;
                 if constexpr (MASKED) { if (out_mask) out_mask[((int64_t)n * Cout + co) * plane + (int64_t)y * W + x] = v > 0.f ? 1 : 0; }
                 if constexpr (OUTB) outb[((int64_t)n * Cout + co) * plane + (int64_t)y * W + x] = (__bf16)v;
@@ -552,7 +485,7 @@ __global__ __launch_bounds__(256) void conv3x3_bf16_splitk_epilogue(
         for (int k = 1; k < ksplit; ++k) v += slab[(int64_t)k * total + i];
         const int co = (int)((i / plane) % Cout);
         v += bias ? bias[co] : 0.f;
-        v = act_bf(v * (scale ? scale[co] : 1.f) + (shift ? shift[co] : 0.f), act, slope);
+        v = act_apply(v * (scale ? scale[co] : 1.f) + (shift ? shift[co] : 0.f), act, slope);
         if (out_mask) out_mask[i] = v > 0.f ? 1 : 0;
         out[i] = v;
     }
@@ -573,7 +506,6 @@ __global__ __launch_bounds__(256) void conv3x3_bf16_splitk_epilogue(
 constexpr int WG_P = 80, WI_P = 112;
 constexpr int WG_BYTES = 2 * 64 * WG_P, WI_BYTES = 4 * 64 * WI_P;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // VEC (W % 4 == 0, 16-B aligned tensors -- every real layer): the tiles are staged with 16-B loads (4 pixels of a row per lane;
 // the two halo columns of the input tile as single dwords).  With one dword per lane the kernel was bound by the rate at which a
@@ -900,51 +832,22 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_bf16_mfma(
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-static inline int grid_1d_bf(int64_t n, int threads)
-{
-    int64_t g = (n + threads - 1) / threads;
-    if (g > 256 * 32) g = 256 * 32;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 int conv3x3_bf16_co_block(int Cout) { return Cout <= 32 ? 32 : 64; }
 
-static inline int64_t packed_bf16_elems(int Cin, int Cout)
-{
-    const int CO = conv3x3_bf16_co_block(Cout);
-    const int ncb = (Cout + CO - 1) / CO, nchunks = (Cin + BKC - 1) / BKC;
-    return (int64_t)ncb * nchunks * 9 * CO * BKC;
-}
+static inline int64_t packed_bf16_elems(int Cin, int Cout) { return PackBf16::side(Cin, Cout).n; }
 
 int64_t conv3x3_bf16_packed_floats(int Cin, int Cout) { return packed_bf16_elems(Cin, Cout) / 2; }
 
 hipError_t launch_pack_weights_3x3_bf16_both(const float* w, float* wp_f, float* wp_t, int Cin, int Cout, hipStream_t s)
 {
-    const int CO_f = conv3x3_bf16_co_block(Cout), CO_t = conv3x3_bf16_co_block(Cin);
-    const int nchunks_f = (Cin + BKC - 1) / BKC, nchunks_t = (Cout + BKC - 1) / BKC;
-    const int64_t n_f = wp_f ? packed_bf16_elems(Cin, Cout) : 0, n_t = wp_t ? packed_bf16_elems(Cout, Cin) : 0;
-    hipLaunchKernelGGL(pack_weights_3x3_bf16_both, dim3(grid_1d_bf(n_f + n_t, 256)), dim3(256), 0, s, w, reinterpret_cast<__bf16*>(wp_f),
-                       reinterpret_cast<__bf16*>(wp_t), Cin, Cout, CO_f, nchunks_f, n_f, CO_t, nchunks_t, n_t);
-    return hipGetLastError();
+    return launch_pack_pair<PackBf16>(w, wp_f, wp_t, Cin, Cout, false, s);
 }
 
-int64_t pack_group_entry_bf16(int Cin, int Cout, int64_t* out)
-{
-    const int CO_f = conv3x3_bf16_co_block(Cout), CO_t = conv3x3_bf16_co_block(Cin);
-    const int nchunks_f = (Cin + BKC - 1) / BKC, nchunks_t = (Cout + BKC - 1) / BKC;
-    out[3] = Cin; out[4] = Cout;
-    out[5] = CO_f; out[6] = nchunks_f; out[7] = (Cout + CO_f - 1) / CO_f; out[8] = packed_bf16_elems(Cin, Cout);
-    out[9] = CO_t; out[10] = nchunks_t; out[11] = (Cin + CO_t - 1) / CO_t; out[12] = packed_bf16_elems(Cout, Cin);
-    return (out[8] + out[12] + 255) / 256;
-}
+int64_t pack_group_entry_bf16(int Cin, int Cout, int64_t* out) { return pack_entry<PackBf16>(Cin, Cout, out); }
 
 hipError_t launch_pack_weights_3x3_bf16_group(const int64_t* table, int n_entries, int64_t total_blocks, hipStream_t s)
 {
-    if (n_entries <= 0 || total_blocks <= 0) return hipSuccess;
-    if (total_blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(pack_weights_3x3_bf16_group, dim3((unsigned)total_blocks), dim3(256), 0, s, table, n_entries);
-    return hipGetLastError();
+    return launch_pack_table<PackBf16>(table, n_entries, total_blocks, s);
 }
 
 bool conv3x3_bf16_supported(int N, int Cin, int H, int W, int Cout)
@@ -1010,8 +913,7 @@ hipError_t launch_conv3x3_bf16_mfma_io(const void* in, int in_bf16, const float*
     // pack
     hipError_t e = hipSuccess;
     if (!prepacked) {
-        e = launch_kernel<pack_weights_3x3_bf16>(dim3(grid_1d_bf(welems, 256)), dim3(256), 0, s, w, wp, Cin, Cout, CO, nchunks, ncb,
-                                                 w_transposed_flipped);
+        e = launch_pack_pair<PackBf16>(w, workspace, nullptr, Cin, Cout, w_transposed_flipped != 0, s);
         if (e != hipSuccess) return e;
     }
     // dispatch: channel block x staging x tensor formats x masks; a bf16 input and masks exist with the 16-byte staging only
@@ -1026,7 +928,7 @@ hipError_t launch_conv3x3_bf16_mfma_io(const void* in, int in_bf16, const float*
     }, CO == 64, vec, in_bf16 != 0, out_bf16 != 0, masked);
     if (e != hipSuccess || ksplit == 1) return e;
     // epilogue: the slice sum
-    return launch_kernel<conv3x3_bf16_splitk_epilogue>(dim3(grid_1d_bf(out_elems, 256)), dim3(256), 0, s, slab, bias, scale, shift,
+    return launch_kernel<conv3x3_bf16_splitk_epilogue>(dim3(grid_1d(out_elems, 256)), dim3(256), 0, s, slab, bias, scale, shift,
                                                        static_cast<float*>(out), out_elems, (int64_t)H * W, Cout, ksplit, act, slope, out_mask);
 }
 

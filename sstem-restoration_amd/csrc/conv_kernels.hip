@@ -26,12 +26,11 @@
 #include <stdlib.h>
 
 #include "conv_kernels.h"
+#include "conv_device.h"
 #include "conv_launch.h"
+#include "conv_pack.h"
 
 namespace sstem {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int KC = 8;                 // input channels per K chunk
 constexpr int KK = KC * 9;            // 72 k-values per chunk
@@ -40,110 +39,28 @@ constexpr int IN_R = TH + 2;          // 10 input rows
 constexpr int IN_PW = 34;             // 32 + 2 halo columns
 constexpr int IN_TILE = KC * IN_R * IN_PW;   // 2720 floats
 
-// "wave-uniform 64-bit base (SGPR pair) + one 32-bit per-lane byte offset" stores: the saddr form, no per-lane 64-bit addresses
-typedef __attribute__((address_space(1))) float gfloat_t;
-template <typename T>
-__device__ __forceinline__ void pin_uniform_ptr(T*& p) { asm volatile("" : "+s"(p)); }
-__device__ __forceinline__ void store_lane(float* ubase, uint32_t lane_byte_off, float v)
-{
-    *reinterpret_cast<gfloat_t*>(reinterpret_cast<uint64_t>(ubase) + lane_byte_off) = v;
-}
-
-// (ConvExtra: conv_kernels.h)
-__device__ __forceinline__ float apply_act(float v, int act, float slope)
-{
-    if (act == 1) return v > 0.f ? v : 0.f;
-    if (act == 2) return v > 0.f ? v : v * slope;
-    return v;
-}
-
 // ---- weight packing: W[co][ci][3][3] -> Wp[cb][chunk][k'][CO], k' = (cl%4)*9+ky*3+kx + 36*(cl/4)
-// (zero-padded in co and ci).  For the transposed use (dgrad / zero-insert ConvTranspose) the
-// source is W[ci][co][3][3] read with the taps flipped.
-__global__ void pack_weights_3x3(const float* __restrict__ w, float* __restrict__ wp, int Cin, int Cout,
-                                 int CO, int nchunks, int ncb, int transposed_flipped)
-{
-    const int64_t total = (int64_t)ncb * nchunks * KK * CO;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (int64_t)gridDim.x * blockDim.x) {
-        const int col = idx % CO;
-        int64_t r = idx / CO;
-        const int kp = r % KK; r /= KK;
-        const int chunk = r % nchunks;
-        const int cb = r / nchunks;
-        const int half = kp / 36, rem = kp % 36;
-        const int cl = rem / 9 + 4 * half, tap = rem % 9;
-        const int ci = chunk * KC + cl, co = cb * CO + col;
-        float v = 0.f;
-        if (ci < Cin && co < Cout) {
-            if (!transposed_flipped) v = w[((int64_t)co * Cin + ci) * 9 + tap];
-            else v = w[((int64_t)ci * Cout + co) * 9 + (8 - tap)];
-        }
-        wp[idx] = v;
+// (zero-padded in co and ci; the decode is pack_f32_slot, conv_pack.h).  For the transposed use (dgrad / zero-insert ConvTranspose)
+// the source is W[ci][co][3][3] read with the taps flipped.
+static_assert(KC == PACK_F32_KC && KK == PACK_F32_KK, "pack_f32_slot decodes this kernel's K chunk");
+namespace {
+struct PackF32 {
+    typedef float elem_t;
+    static PackSide side(int cin, int cout)
+    {
+        const int CO = conv3x3_co_block(cout);
+        const int ncb = (cout + CO - 1) / CO, nchunks = (cin + KC - 1) / KC;
+        return PackSide{CO, nchunks, ncb, (int64_t)ncb * nchunks * KK * CO};
     }
-}
-
-// Both packings of one layer's weights in ONE launch (training: the forward packing and the transposed + flipped one its data
-// gradient needs -- two launches per layer and step before): indices [0, n_fwd) are the forward layout, the rest the transposed one
-// of the (Cout -> Cin) problem.  Same element function as pack_weights_3x3.
-__global__ void pack_weights_3x3_both(const float* __restrict__ w, float* __restrict__ wp_f, float* __restrict__ wp_t, int Cin,
-                                      int Cout, int CO_f, int nchunks_f, int ncb_f, int64_t n_fwd, int CO_t, int nchunks_t,
-                                      int ncb_t, int64_t n_t)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_fwd + n_t; i += (int64_t)gridDim.x * blockDim.x) {
-        const bool t = i >= n_fwd;
-        const int64_t idx = t ? i - n_fwd : i;
-        const int CO = t ? CO_t : CO_f, nchunks = t ? nchunks_t : nchunks_f;
-        const int cin = t ? Cout : Cin, cout = t ? Cin : Cout;          // sizes of the convolution this packing serves
-        const int col = idx % CO;
-        int64_t r = idx / CO;
-        const int kp = r % KK; r /= KK;
-        const int chunk = r % nchunks;
-        const int cb = r / nchunks;
-        const int half = kp / 36, rem = kp % 36;
-        const int cl = rem / 9 + 4 * half, tap = rem % 9;
-        const int ci = chunk * KC + cl, co = cb * CO + col;
-        float v = 0.f;
-        if (ci < cin && co < cout) v = t ? w[((int64_t)ci * cout + co) * 9 + (8 - tap)] : w[((int64_t)co * cin + ci) * 9 + tap];
-        (t ? wp_t : wp_f)[idx] = v;
+    static __device__ __forceinline__ float slot(const float* __restrict__ w, int64_t idx, int cin, int cout, int CO, int nchunks,
+                                                 bool transposed_flipped)
+    {
+        const PackF32Slot k = pack_f32_slot(idx, CO, nchunks);
+        if (k.ci >= cin || k.co >= cout) return 0.f;
+        return transposed_flipped ? w[((int64_t)k.ci * cout + k.co) * 9 + (8 - k.tap)] : w[((int64_t)k.co * cin + k.ci) * 9 + k.tap];
     }
-}
-
-// Both packings of MANY layers in one launch (training: after the optimiser step every layer's weights have changed; one pack
-// launch per layer and step was 19 launches of the 2-sample fusion step and 46 of the IFNet step).  table[e] = 16 int64: w, wp_f,
-// wp_t, Cin, Cout, CO_f, nchunks_f, ncb_f, n_fwd, CO_t, nchunks_t, ncb_t, n_t, first 256-thread block of the entry (ascending), 0, 0
-// -- the layout numbers come from pack_group_entry below, i.e. from the same functions the per-layer launch uses.
-__global__ __launch_bounds__(256) void pack_weights_3x3_group(const int64_t* __restrict__ table, int n_entries)
-{
-    int lo = 0, hi = n_entries - 1;                       // last entry whose first block is <= blockIdx.x
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[(int64_t)mid * 16 + 13] <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const int64_t* en = table + (int64_t)lo * 16;
-    const float* w = reinterpret_cast<const float*>(en[0]);
-    float* wp_f = reinterpret_cast<float*>(en[1]);
-    float* wp_t = reinterpret_cast<float*>(en[2]);
-    const int Cin = (int)en[3], Cout = (int)en[4];
-    const int64_t n_fwd = en[8], n_t = en[12];
-    const int64_t i = ((int64_t)blockIdx.x - en[13]) * 256 + threadIdx.x;
-    if (i >= n_fwd + n_t) return;
-    const bool t = i >= n_fwd;
-    const int64_t idx = t ? i - n_fwd : i;
-    const int CO = (int)(t ? en[9] : en[5]), nchunks = (int)(t ? en[10] : en[6]);
-    const int cin = t ? Cout : Cin, cout = t ? Cin : Cout;
-    const int col = idx % CO;
-    int64_t r = idx / CO;
-    const int kp = r % KK; r /= KK;
-    const int chunk = r % nchunks;
-    const int cb = r / nchunks;
-    const int half = kp / 36, rem = kp % 36;
-    const int cl = rem / 9 + 4 * half, tap = rem % 9;
-    const int ci = chunk * KC + cl, co = cb * CO + col;
-    float v = 0.f;
-    if (ci < cin && co < cout) v = t ? w[((int64_t)ci * cout + co) * 9 + (8 - tap)] : w[((int64_t)co * cin + ci) * 9 + tap];
-    (t ? wp_t : wp_f)[idx] = v;
-}
+};
+}  // namespace
 
 template <int COT, int WT = 32, int RPW = 2>
 __global__ __launch_bounds__(256, COT == 1 ? 4 : 2) void conv3x3_mfma(
@@ -408,7 +325,7 @@ __global__ __launch_bounds__(256, COT == 1 ? 4 : 2) void conv3x3_mfma(
                         for (int rr = 0; rr < RPW; ++rr) {
                             const float* rp = rchp + rr * RM * W;
                             pin_uniform_ptr(rp);
-                            if (live) rv[rr] = *reinterpret_cast<const gfloat_t*>(reinterpret_cast<uint64_t>(rp) + lane_off);
+                            if (live) rv[rr] = load_lane(rp, lane_off);
                         }
                     }
 #pragma unroll
@@ -453,7 +370,7 @@ __global__ __launch_bounds__(256, COT == 1 ? 4 : 2) void conv3x3_mfma(
                 if (y < H && x < W) {
                     float v = acc[t][rr][q] + bs;
                     v = v * sc + sh;
-                    v = apply_act(v, act, slope);
+                    v = act_apply(v, act, slope);
                     const int64_t o = ((int64_t)n * Cout + co) * plane + (int64_t)y * W + x;
                     if (ex.residual) v = (v + ex.residual[o]) * ex.res_scale;
                     out[o] = v;
@@ -475,7 +392,7 @@ __global__ __launch_bounds__(256) void conv3x3_splitk_epilogue(
         const int co = (int)((i / plane) % Cout);
         v += bias ? bias[co] : 0.f;
         v = v * (scale ? scale[co] : 1.f) + (shift ? shift[co] : 0.f);
-        v = apply_act(v, act, slope);
+        v = act_apply(v, act, slope);
         if (residual) v = (v + residual[i]) * res_scale;
         out[i] = v;
     }
@@ -512,7 +429,7 @@ __global__ __launch_bounds__(256) void conv2d_direct(
         }
         float v = acc + (bias ? bias[co] : 0.f);
         v = v * (scale ? scale[co] : 1.f) + (shift ? shift[co] : 0.f);
-        out[idx] = apply_act(v, act, slope);
+        out[idx] = act_apply(v, act, slope);
     }
 }
 
@@ -550,7 +467,7 @@ __global__ __launch_bounds__(256) void convT3x3s2_direct(
         }
         float v = acc + (bias ? bias[co] : 0.f);
         v = v * (scale ? scale[co] : 1.f) + (shift ? shift[co] : 0.f);
-        out[idx] = apply_act(v, act, slope);
+        out[idx] = act_apply(v, act, slope);
     }
 }
 
@@ -1242,14 +1159,6 @@ __global__ __launch_bounds__(64 * RED_KG) void wgrad_reduce_group(const WgradRed
 }
 
 // ---- host launchers ------------------------------------------------------------------------
-static inline int grid_1d(int64_t n, int threads)
-{
-    int64_t g = (n + threads - 1) / threads;
-    if (g > 256 * 32) g = 256 * 32;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 // output channels per workgroup.  Measured on MI355X: 32-channel blocks (40 KB LDS, 4 workgroups per CU) beat 64 on every layer shape
 int conv3x3_co_block(int Cout)
 {
@@ -1333,8 +1242,7 @@ hipError_t launch_conv3x3_mfma(const float* in, const float* w, const float* bia
     // pack
     hipError_t e = hipSuccess;
     if (!prepacked) {
-        e = launch_kernel<pack_weights_3x3>(dim3(grid_1d(wtotal, 256)), dim3(256), 0, s, w, workspace, Cin, Cout, CO, nchunks, ncb,
-                                            w_transposed_flipped);
+        e = launch_pack_pair<PackF32>(w, workspace, nullptr, Cin, Cout, w_transposed_flipped != 0, s);
         if (e != hipSuccess) return e;
     }
     // dispatch: tile width x MFMA rows per wave
@@ -1351,33 +1259,14 @@ hipError_t launch_conv3x3_mfma(const float* in, const float* w, const float* bia
 
 hipError_t launch_pack_weights_3x3_both(const float* w, float* wp_f, float* wp_t, int Cin, int Cout, hipStream_t s)
 {
-    const int CO_f = conv3x3_co_block(Cout), CO_t = conv3x3_co_block(Cin);
-    const int ncb_f = (Cout + CO_f - 1) / CO_f, nchunks_f = (Cin + KC - 1) / KC;
-    const int ncb_t = (Cin + CO_t - 1) / CO_t, nchunks_t = (Cout + KC - 1) / KC;
-    const int64_t n_f = wp_f ? (int64_t)ncb_f * nchunks_f * KK * CO_f : 0, n_t = wp_t ? (int64_t)ncb_t * nchunks_t * KK * CO_t : 0;
-    hipLaunchKernelGGL(pack_weights_3x3_both, dim3(grid_1d(n_f + n_t, 256)), dim3(256), 0, s, w, wp_f, wp_t, Cin, Cout, CO_f,
-                       nchunks_f, ncb_f, n_f, CO_t, nchunks_t, ncb_t, n_t);
-    return hipGetLastError();
+    return launch_pack_pair<PackF32>(w, wp_f, wp_t, Cin, Cout, false, s);
 }
 
-// layout numbers of one entry of the group-pack table (out[3..12]); returns the 256-thread blocks the entry needs
-int64_t pack_group_entry(int Cin, int Cout, int64_t* out)
-{
-    const int CO_f = conv3x3_co_block(Cout), CO_t = conv3x3_co_block(Cin);
-    const int ncb_f = (Cout + CO_f - 1) / CO_f, nchunks_f = (Cin + KC - 1) / KC;
-    const int ncb_t = (Cin + CO_t - 1) / CO_t, nchunks_t = (Cout + KC - 1) / KC;
-    out[3] = Cin; out[4] = Cout;
-    out[5] = CO_f; out[6] = nchunks_f; out[7] = ncb_f; out[8] = (int64_t)ncb_f * nchunks_f * KK * CO_f;
-    out[9] = CO_t; out[10] = nchunks_t; out[11] = ncb_t; out[12] = (int64_t)ncb_t * nchunks_t * KK * CO_t;
-    return (out[8] + out[12] + 255) / 256;
-}
+int64_t pack_group_entry(int Cin, int Cout, int64_t* out) { return pack_entry<PackF32>(Cin, Cout, out); }
 
 hipError_t launch_pack_weights_3x3_group(const int64_t* table, int n_entries, int64_t total_blocks, hipStream_t s)
 {
-    if (n_entries <= 0 || total_blocks <= 0) return hipSuccess;
-    if (total_blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(pack_weights_3x3_group, dim3((unsigned)total_blocks), dim3(256), 0, s, table, n_entries);
-    return hipGetLastError();
+    return launch_pack_table<PackF32>(table, n_entries, total_blocks, s);
 }
 
 // 1 x 1 convolutions with a handful of output channels (the OutConv of the SP U-Nets, networks.py:238: 64 -> 1 at full resolution;
@@ -1414,7 +1303,7 @@ __global__ __launch_bounds__(256) void conv1x1_stream(const float* __restrict__ 
             for (int e = 0; e < 4; ++e) {
                 float v = acc[co][e] + (bias ? bias[co] : 0.f);
                 v = v * (scale ? scale[co] : 1.f) + (shift ? shift[co] : 0.f);
-                r[e] = apply_act(v, act, slope);
+                r[e] = act_apply(v, act, slope);
             }
             reinterpret_cast<f4*>(out + ((int64_t)n * COUT + co) * plane)[q] = r;
         }
@@ -1503,7 +1392,7 @@ __global__ __launch_bounds__(256) void conv3x3_stream_small(const float* __restr
                 f4 r4;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float t = apply_act((acc[co][o][e] + bs) * sc + sh, act, slope);
+                    const float t = act_apply((acc[co][o][e] + bs) * sc + sh, act, slope);
                     r4[e] = t;
                     vmax = fmaxf(vmax, fabsf(t));
                 }
@@ -1607,7 +1496,7 @@ __global__ __launch_bounds__(256) void conv3x3_first_u8(const uint8_t* __restric
                 f4 r4;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float t = apply_act((acc[co][o][e] + bs) * 1.f + 0.f, act, slope);      // (the fp32 kernel's epilogue with scale 1, shift 0)
+                    const float t = act_apply((acc[co][o][e] + bs) * 1.f + 0.f, act, slope);      // (the fp32 kernel's epilogue with scale 1, shift 0)
                     r4[e] = t;
                     vmax = fmaxf(vmax, fabsf(t));
                 }

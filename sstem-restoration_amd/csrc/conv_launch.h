@@ -33,6 +33,15 @@ inline int wgrad_slabs(int target, int64_t blocks, int64_t ntiles, int min_tiles
     return (int)k;
 }
 
+// workgroups of `threads` for the grid-stride kernels over n elements: at most 8192, at least one
+inline int grid_1d(int64_t n, int threads)
+{
+    int64_t g = (n + threads - 1) / threads;
+    if (g > 256 * 32) g = 256 * 32;
+    if (g < 1) g = 1;
+    return (int)g;
+}
+
 // One launch of one kernel instance.  The instance is the template argument itself, not its type: two instances with the same
 // signature share a type and would share the flag below.  Dynamic LDS above the 64 KB default needs
 // hipFuncAttributeMaxDynamicSharedMemorySize raised, once per instance and device: devices 0-63 remember the largest size they were

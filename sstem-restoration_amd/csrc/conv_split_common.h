@@ -4,12 +4,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "conv_device.h"
+
 namespace sstem {
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 typedef uint64_t u64x2v __attribute__((ext_vector_type(2)));
 
@@ -27,26 +27,7 @@ constexpr int SIN_PW = STW + 2;
 constexpr int SIN_BYTES = 11200;              // 2 halves x 10 rows x 35 slots x 16 B (32-wide tiles; 18 x 19 slots x 2 for 16-wide: 10944)
 constexpr uint32_t S_OOB = 0x80000000u;
 
-typedef __attribute__((address_space(1))) float gfloat_t;
 typedef __attribute__((address_space(1))) uint8_t gbyte_t;
-template <typename T>
-__device__ __forceinline__ void pin_uptr(T*& p) { asm volatile("" : "+s"(p)); }
-__device__ __forceinline__ void st_lane(float* ubase, uint32_t lane_byte_off, float v)
-{
-    *reinterpret_cast<gfloat_t*>(reinterpret_cast<uint64_t>(ubase) + lane_byte_off) = v;
-}
-__device__ __forceinline__ float ld_lane(const float* ubase, uint32_t lane_byte_off)
-{
-    return *reinterpret_cast<const gfloat_t*>(reinterpret_cast<uint64_t>(ubase) + lane_byte_off);
-}
-__device__ __forceinline__ void pin_s(uint32_t& v) { asm volatile("" : "+s"(v)); }
-
-__device__ __forceinline__ float act_s(float v, int act, float slope)
-{
-    if (act == 1) return v > 0.f ? v : 0.f;
-    if (act == 2) return v > 0.f ? v : v * slope;
-    return v;
-}
 
 // x -> P bf16 pieces with x = sum of the pieces (exactly for P = 3; to 2^-17 relative for P = 2)
 template <int P>
@@ -91,11 +72,11 @@ __device__ __forceinline__ float scale_of_exponent(int e) { return __builtin_bit
 // maximum of the slots of an amax word, by the calling wave (uniform result): 4 KB, four 16-byte loads per lane
 __device__ __forceinline__ float amax_word_max(const float* __restrict__ word)
 {
-    const f32x4v* w4 = reinterpret_cast<const f32x4v*>(word) + (threadIdx.x & 63);
+    const f32x4* w4 = reinterpret_cast<const f32x4*>(word) + (threadIdx.x & 63);
     float m = 0.f;
 #pragma unroll
     for (int k = 0; k < AMAX_SLOTS / 256; ++k) {
-        const f32x4v v = w4[k * 64];
+        const f32x4 v = w4[k * 64];
         m = fmaxf(fmaxf(m, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
     }
 #pragma unroll

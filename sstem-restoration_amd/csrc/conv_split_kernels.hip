@@ -29,6 +29,7 @@
 #include "conv_kernels.h"
 #include "conv_split_common.h"
 #include "conv_launch.h"
+#include "conv_pack.h"
 
 // developer ablation builds of conv3x3_split_mfma (wrong results; tools/build_ablate_split.sh): 1 no per-item LDS reads of the B operand,
 // 2 no staging commit (split + LDS stores), 4 no staging loads, 8 no A-fragment loads after the first, 64 no epilogue stores (whole tiles);
@@ -52,7 +53,7 @@ __global__ __launch_bounds__(256) void amax_kernel(const float* __restrict__ x, 
     float m = 0.f;
     const int64_t n4 = (reinterpret_cast<uintptr_t>(x) & 15) == 0 ? n / 4 : 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        const f32x4v v = reinterpret_cast<const f32x4v*>(x)[i];
+        const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
         m = fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
     }
     for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) m = fmaxf(m, fabsf(x[i]));
@@ -73,35 +74,47 @@ __host__ __device__ inline bool split_tail_chunk(int cin, int P, bool f16 = fals
     return SSTEM_SPLIT_TAIL && (P == 3 || f16) && cin > 16 && cin % 16 >= 1 && cin % 16 <= 4;
 }
 
-// one element of a packed weight image [chunk][piece][tap][output channel, padded to COP][16 input channels]: the layout does not
-// depend on the output-channel block a launch chooses (32 or 64 per workgroup, by grid size)
+// One slot of a packed weight image [chunk][piece][tap][output channel, padded to COP][16 input channels] (the layout does not depend on
+// the output-channel block a launch chooses, 32 or 64 per workgroup, by grid size): its axes and the fp32 weight that belongs there.
+// PA = length of the piece axis of `idx`: P for an element index, 1 for an index that counts weights (pack_pair_f16).
+struct SplitSlot { int chunk, piece, tap, co, cl; float v; };
+template <int P, bool F16, int PA = P>
+__device__ __forceinline__ SplitSlot split_slot(const float* __restrict__ w, int64_t idx, int cin, int cout, int COP, int nchunks,
+                                                bool transposed_flipped)
+{
+    SplitSlot k;
+    k.cl = idx % SKC;
+    int64_t r = idx / SKC;
+    k.co = r % COP; r /= COP;
+    k.tap = r % 9; r /= 9;
+    k.piece = r % PA;
+    k.chunk = (int)(r / PA);
+    int ci = k.chunk * SKC + k.cl;
+    int wtap = k.tap;
+    bool live = true;
+    if (split_tail_chunk(cin, P, F16) && k.chunk == nchunks - 1) {       // slots 0..2 of the tap axis hold the tap rows, the rest is not read
+        const int kx = k.cl >> 2;
+        ci = k.chunk * SKC + (k.cl & 3);
+        wtap = k.tap * 3 + kx;
+        live = k.tap < 3 && kx < 3;
+    }
+    k.v = 0.f;
+    if (live && ci < cin && k.co < cout)
+        k.v = transposed_flipped ? w[((int64_t)ci * cout + k.co) * 9 + (8 - wtap)] : w[((int64_t)k.co * cin + ci) * 9 + wtap];
+    return k;
+}
+
+// one element of a packed weight image
 template <int P, bool F16 = false>
 __device__ __forceinline__ __bf16 packed_weight(const float* __restrict__ w, int64_t idx, int cin, int cout, int COP, int nchunks,
                                                 bool transposed_flipped, float wscale = 1.f)
 {
-    const int cl = idx % SKC;
-    int64_t r = idx / SKC;
-    const int co = r % COP; r /= COP;
-    const int tap = r % 9; r /= 9;
-    const int piece = r % P; r /= P;
-    const int chunk = (int)r;
-    int ci = chunk * SKC + cl;
-    int wtap = tap;
-    bool live = true;
-    if (split_tail_chunk(cin, P, F16) && chunk == nchunks - 1) {         // slots 0..2 of the tap axis hold the tap rows, the rest is not read
-        const int kx = cl >> 2;
-        ci = chunk * SKC + (cl & 3);
-        wtap = tap * 3 + kx;
-        live = tap < 3 && kx < 3;
-    }
-    float v = 0.f;
-    if (live && ci < cin && co < cout)
-        v = transposed_flipped ? w[((int64_t)ci * cout + co) * 9 + (8 - wtap)] : w[((int64_t)co * cin + ci) * 9 + wtap];
+    const SplitSlot k = split_slot<P, F16>(w, idx, cin, cout, COP, nchunks, transposed_flipped);
     __bf16 pc[P];
-    if constexpr (F16) split_pieces_f16(v * wscale, pc); else split_pieces<P>(v, pc);
+    if constexpr (F16) split_pieces_f16(k.v * wscale, pc); else split_pieces<P>(k.v, pc);
     __bf16 res = pc[0];
 #pragma unroll
-    for (int p = 1; p < P; ++p) if (piece == p) res = pc[p];
+    for (int p = 1; p < P; ++p) if (k.piece == p) res = pc[p];
     return res;
 }
 
@@ -111,26 +124,10 @@ __device__ __forceinline__ __bf16 packed_weight(const float* __restrict__ w, int
 __device__ __forceinline__ void pack_pair_f16(const float* __restrict__ w, __bf16* __restrict__ wp, int64_t j, int cin, int cout, int COP,
                                               int nchunks, bool transposed_flipped, float wscale)
 {
-    const int cl = j % SKC;
-    int64_t r = j / SKC;
-    const int co = r % COP; r /= COP;
-    const int tap = r % 9;
-    const int chunk = (int)(r / 9);
-    int ci = chunk * SKC + cl;
-    int wtap = tap;
-    bool live = true;
-    if (split_tail_chunk(cin, 2, true) && chunk == nchunks - 1) {
-        const int kx = cl >> 2;
-        ci = chunk * SKC + (cl & 3);
-        wtap = tap * 3 + kx;
-        live = tap < 3 && kx < 3;
-    }
-    float v = 0.f;
-    if (live && ci < cin && co < cout)
-        v = transposed_flipped ? w[((int64_t)ci * cout + co) * 9 + (8 - wtap)] : w[((int64_t)co * cin + ci) * 9 + wtap];
+    const SplitSlot k = split_slot<2, true, 1>(w, j, cin, cout, COP, nchunks, transposed_flipped);
     __bf16 pc[2];
-    split_pieces_f16(v * wscale, pc);
-    const int64_t first = (((int64_t)chunk * 2) * 9 + tap) * COP * SKC + (int64_t)co * SKC + cl;
+    split_pieces_f16(k.v * wscale, pc);
+    const int64_t first = (((int64_t)k.chunk * 2) * 9 + k.tap) * COP * SKC + (int64_t)k.co * SKC + k.cl;
     wp[first] = pc[0];
     wp[first + (int64_t)9 * COP * SKC] = pc[1];
 }
@@ -165,18 +162,13 @@ __global__ void pack_weights_3x3_split_f16_both(const float* __restrict__ w, __b
     }
 }
 
-// many layers in one go (fp16 pieces): table entries as pack_weights_3x3_split_group's, plus [14] = the entry's first block in the
+// many layers in one go (fp16 pieces): table entries as pack_weights_table's (conv_pack.h), plus [14] = the entry's first block in the
 // bound launch (4096 weights per block) and [15] = the address of the float that launch raises to the layer's largest magnitude
 // (zeroed by the launcher; non-negative floats order like their bit patterns)
 constexpr int AMAX_GROUP_ELEMS = 4096;
 __global__ __launch_bounds__(256) void amax_weights_group(const int64_t* __restrict__ table, int n_entries)
 {
-    int lo = 0, hi = n_entries - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[(int64_t)mid * 16 + 14] <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const int64_t* en = table + (int64_t)lo * 16;
+    const int64_t* en = pack_table_entry(table, n_entries, 14);
     const float* w = reinterpret_cast<const float*>(en[0]);
     const int64_t n = en[3] * en[4] * 9;
     const int64_t base = ((int64_t)blockIdx.x - en[14]) * AMAX_GROUP_ELEMS;
@@ -196,12 +188,7 @@ __global__ __launch_bounds__(256) void amax_weights_group(const int64_t* __restr
 }
 __global__ __launch_bounds__(256) void pack_weights_3x3_split_f16_group(const int64_t* __restrict__ table, int n_entries)
 {
-    int lo = 0, hi = n_entries - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[(int64_t)mid * 16 + 13] <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const int64_t* en = table + (int64_t)lo * 16;
+    const int64_t* en = pack_table_entry(table, n_entries, 13);
     const float* w = reinterpret_cast<const float*>(en[0]);
     __bf16* wp_f = reinterpret_cast<__bf16*>(en[1]);
     __bf16* wp_t = reinterpret_cast<__bf16*>(en[2]);
@@ -215,40 +202,6 @@ __global__ __launch_bounds__(256) void pack_weights_3x3_split_f16_group(const in
     if (j >= h_fwd + h_t) return;
     if (j >= h_fwd) pack_pair_f16(w, wp_t + 8, j - h_fwd, Cout, Cin, (int)en[9], (int)en[10], true, wscale);
     else pack_pair_f16(w, wp_f + 8, j, Cin, Cout, (int)en[5], (int)en[6], false, wscale);
-}
-
-// forward packing of [Cout,Cin,3,3] and / or the transposed + flipped packing its data gradient uses (either may be null: n = 0)
-template <int P>
-__global__ void pack_weights_3x3_split_both(const float* __restrict__ w, __bf16* __restrict__ wp_f, __bf16* __restrict__ wp_t, int Cin,
-                                            int Cout, int COP_f, int nchunks_f, int64_t n_fwd, int COP_t, int nchunks_t, int64_t n_t,
-                                            int fwd_is_transposed)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_fwd + n_t; i += (int64_t)gridDim.x * blockDim.x) {
-        const bool t = i >= n_fwd;
-        if (t) wp_t[i - n_fwd] = packed_weight<P>(w, i - n_fwd, Cout, Cin, COP_t, nchunks_t, true);
-        else wp_f[i] = packed_weight<P>(w, i, Cin, Cout, COP_f, nchunks_f, fwd_is_transposed != 0);
-    }
-}
-
-// many layers in one launch: the table of pack_weights_3x3_group (conv_kernels.hip), entries from pack_group_entry_split
-template <int P>
-__global__ __launch_bounds__(256) void pack_weights_3x3_split_group(const int64_t* __restrict__ table, int n_entries)
-{
-    int lo = 0, hi = n_entries - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[(int64_t)mid * 16 + 13] <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const int64_t* en = table + (int64_t)lo * 16;
-    const float* w = reinterpret_cast<const float*>(en[0]);
-    __bf16* wp_f = reinterpret_cast<__bf16*>(en[1]);
-    __bf16* wp_t = reinterpret_cast<__bf16*>(en[2]);
-    const int Cin = (int)en[3], Cout = (int)en[4];
-    const int64_t n_fwd = en[8], n_t = en[12];
-    const int64_t i = ((int64_t)blockIdx.x - en[13]) * 256 + threadIdx.x;
-    if (i >= n_fwd + n_t) return;
-    if (i >= n_fwd) wp_t[i - n_fwd] = packed_weight<P>(w, i - n_fwd, Cout, Cin, (int)en[9], (int)en[10], true);
-    else wp_f[i] = packed_weight<P>(w, i, Cin, Cout, (int)en[5], (int)en[6], false);
 }
 
 // MASKED: in_mask (nullable, [N,Cin,H,W] bytes) zeroes the input elements whose byte is 0 while they are staged -- the data gradient of
@@ -462,7 +415,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_mfma(
     };
     const uint32_t vvoff = tile_voff(X0, Y0);
     const char* in_n = reinterpret_cast<const char*>(in) + (int64_t)n * Cin * plane * 4;
-    f32x4v stg4[DEEP ? 2 : 1][VEC ? 8 : 1];                                         // DEEP: two sets, a tile's loads two steps ahead
+    f32x4 stg4[DEEP ? 2 : 1][VEC ? 8 : 1];                                         // DEEP: two sets, a tile's loads two steps ahead
     uint32_t mk4[(VEC && MASKED) ? 8 : 1];                                         // the mask bytes of the lane's four pixels, per channel
     // in_img: the image's first byte (uniform), voff_t: tile_voff of the tile the chunk belongs to
     typedef std::integral_constant<int, 0> S0;
@@ -486,8 +439,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_mfma(
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const bool chan = cl_lim >= SKC || vhalf * 8 + i < cl_lim;             // uniform
-                f32x4v v = {0.f, 0.f, 0.f, 0.f};
-                if (chan) v = *reinterpret_cast<const f32x4v*>(pc + (int64_t)i * plane4 + vsafe);
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                if (chan) v = *reinterpret_cast<const f32x4*>(pc + (int64_t)i * plane4 + vsafe);
                 stg4[SET][VEC ? i : 0] = v;
             }
             return;
@@ -502,7 +455,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_mfma(
         const rsrc_t rch = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(pcs), 0, (int)((uint32_t)live_ch * plane4), 0x00020000);
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-            stg4[SET][VEC ? i : 0] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rch, (int)voff_t, (int)((uint32_t)i * plane4), 0));
+            stg4[SET][VEC ? i : 0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rch, (int)voff_t, (int)((uint32_t)i * plane4), 0));
     };
     auto commit_px_v = [&](int buf, int j, int chunk, uint32_t voff_t, auto set_tag) __attribute__((always_inline)) {      // pixel j of the lane's four
         constexpr int SET = decltype(set_tag)::value;
@@ -921,7 +874,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_mfma(
                     o = (((int64_t)n * ct_c + (co - par * ct_c)) * 2 * H + 2 * y + (par >> 1)) * 2 * W + 2 * x + (par & 1);
                 }
                 float v = acc[rr][q] + bs;
-                v = act_s(v * sc + sh, act, slope);
+                v = act_apply(v * sc + sh, act, slope);
                 if constexpr (MASKED) { if (out_mask) out_mask[o] = v > 0.f ? 1 : 0; }
                 if (residual) v = (v + residual[o]) * res_scale;
                 out[(!CT && out_blocked) ? (int64_t)n * o_stride + (int64_t)y * o_row + ((int64_t)(x >> 6) * Cout + co) * 64 + (x & 63)
@@ -1058,7 +1011,7 @@ __global__ __launch_bounds__(256) void conv3x3_split_splitk_epilogue(
         for (int k = 1; k < ksplit; ++k) v += slab[(int64_t)k * total + i];
         const int co = (int)((i / plane) % Cout);
         v += bias ? bias[co] : 0.f;
-        v = act_s(v * (scale ? scale[co] : 1.f) + (shift ? shift[co] : 0.f), act, slope);
+        v = act_apply(v * (scale ? scale[co] : 1.f) + (shift ? shift[co] : 0.f), act, slope);
         if (out_mask) out_mask[i] = v > 0.f ? 1 : 0;
         if (residual) v = (v + residual[i]) * res_scale;
         out[i] = v;
@@ -1068,14 +1021,6 @@ __global__ __launch_bounds__(256) void conv3x3_split_splitk_epilogue(
     if (out_amax) amax_word_update(out_amax, vmax, blockIdx.x, red);
 }
 
-inline int grid_1d_s(int64_t n, int threads)
-{
-    int64_t g = (n + threads - 1) / threads;
-    if (g > 256 * 32) g = 256 * 32;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 inline int split_cop(int Cout) { return Cout <= 32 ? 32 : (Cout + 63) / 64 * 64; }      // padded output channels of the packed weights
 
 inline int64_t packed_split_elems(int Cin, int Cout, int P)
@@ -1083,6 +1028,22 @@ inline int64_t packed_split_elems(int Cin, int Cout, int P)
     const int nchunks = (Cin + SKC - 1) / SKC;
     return (int64_t)nchunks * P * 9 * split_cop(Cout) * SKC;
 }
+
+// the bf16-piece layouts (P = 2: X3, P = 3: X6); packed_weight is the slot function
+template <int P>
+struct PackSplit {
+    typedef __bf16 elem_t;
+    static PackSide side(int cin, int cout)
+    {
+        const int COP = split_cop(cout);
+        return PackSide{COP, (cin + SKC - 1) / SKC, (cout + COP - 1) / COP, packed_split_elems(cin, cout, P)};
+    }
+    static __device__ __forceinline__ __bf16 slot(const float* __restrict__ w, int64_t idx, int cin, int cout, int COP, int nchunks,
+                                                  bool transposed_flipped)
+    {
+        return packed_weight<P>(w, idx, cin, cout, COP, nchunks, transposed_flipped);
+    }
+};
 
 // Output channels per workgroup and K slices: a pure function of the problem size (launcher and workspace query).  64 channels per
 // workgroup (two waves share every input fragment; 32 per workgroup for more workgroups on small grids measured 3-8 % slower on the
@@ -1128,7 +1089,7 @@ int64_t conv3x3_split_packed_floats(int Cin, int Cout, int pieces, int f16)
 hipError_t launch_amax(const float* x, int64_t n, float* word, hipStream_t s)
 {
     if (n <= 0) return hipSuccess;
-    int g = grid_1d_s((n + 3) / 4, 256);                 // one atomic per workgroup, one slot each
+    int g = grid_1d((n + 3) / 4, 256);                   // one atomic per workgroup, one slot each
     if (g > AMAX_SLOTS) g = AMAX_SLOTS;
     hipLaunchKernelGGL(amax_kernel, dim3(g), dim3(256), 0, s, x, n, word);
     return hipGetLastError();
@@ -1146,35 +1107,19 @@ int64_t conv3x3_split_forward_workspace_floats(int N, int Cin, int H, int W, int
 
 hipError_t launch_pack_weights_3x3_split_both(const float* w, float* wp_f, float* wp_t, int Cin, int Cout, int pieces, hipStream_t s)
 {
-    const int CO_f = split_cop(Cout), CO_t = split_cop(Cin);
-    const int nchunks_f = (Cin + SKC - 1) / SKC, nchunks_t = (Cout + SKC - 1) / SKC;
-    const int64_t n_f = wp_f ? packed_split_elems(Cin, Cout, pieces) : 0, n_t = wp_t ? packed_split_elems(Cout, Cin, pieces) : 0;
-    if (pieces == 3)
-        hipLaunchKernelGGL(pack_weights_3x3_split_both<3>, dim3(grid_1d_s(n_f + n_t, 256)), dim3(256), 0, s, w, reinterpret_cast<__bf16*>(wp_f),
-                           reinterpret_cast<__bf16*>(wp_t), Cin, Cout, CO_f, nchunks_f, n_f, CO_t, nchunks_t, n_t, 0);
-    else
-        hipLaunchKernelGGL(pack_weights_3x3_split_both<2>, dim3(grid_1d_s(n_f + n_t, 256)), dim3(256), 0, s, w, reinterpret_cast<__bf16*>(wp_f),
-                           reinterpret_cast<__bf16*>(wp_t), Cin, Cout, CO_f, nchunks_f, n_f, CO_t, nchunks_t, n_t, 0);
-    return hipGetLastError();
+    return pieces == 3 ? launch_pack_pair<PackSplit<3>>(w, wp_f, wp_t, Cin, Cout, false, s)
+                       : launch_pack_pair<PackSplit<2>>(w, wp_f, wp_t, Cin, Cout, false, s);
 }
 
 int64_t pack_group_entry_split(int Cin, int Cout, int pieces, int64_t* out)
 {
-    const int CO_f = split_cop(Cout), CO_t = split_cop(Cin);
-    const int nchunks_f = (Cin + SKC - 1) / SKC, nchunks_t = (Cout + SKC - 1) / SKC;
-    out[3] = Cin; out[4] = Cout;
-    out[5] = CO_f; out[6] = nchunks_f; out[7] = (Cout + CO_f - 1) / CO_f; out[8] = packed_split_elems(Cin, Cout, pieces);
-    out[9] = CO_t; out[10] = nchunks_t; out[11] = (Cin + CO_t - 1) / CO_t; out[12] = packed_split_elems(Cout, Cin, pieces);
-    return (out[8] + out[12] + 255) / 256;
+    return pieces == 3 ? pack_entry<PackSplit<3>>(Cin, Cout, out) : pack_entry<PackSplit<2>>(Cin, Cout, out);
 }
 
 hipError_t launch_pack_weights_3x3_split_group(const int64_t* table, int n_entries, int64_t total_blocks, int pieces, hipStream_t s)
 {
-    if (n_entries <= 0 || total_blocks <= 0) return hipSuccess;
-    if (total_blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (pieces == 3) hipLaunchKernelGGL(pack_weights_3x3_split_group<3>, dim3((unsigned)total_blocks), dim3(256), 0, s, table, n_entries);
-    else hipLaunchKernelGGL(pack_weights_3x3_split_group<2>, dim3((unsigned)total_blocks), dim3(256), 0, s, table, n_entries);
-    return hipGetLastError();
+    return pieces == 3 ? launch_pack_table<PackSplit<3>>(table, n_entries, total_blocks, s)
+                       : launch_pack_table<PackSplit<2>>(table, n_entries, total_blocks, s);
 }
 
 // fp16 pieces of a recorded layer, both orientations: [header][image][amax word of the weights] in each workspace (the word of the
@@ -1182,17 +1127,17 @@ hipError_t launch_pack_weights_3x3_split_group(const int64_t* table, int n_entri
 hipError_t launch_pack_weights_3x3_split_f16_both(const float* w, float* wp_f, float* wp_t, int Cin, int Cout, hipStream_t s)
 {
     if (!wp_f && !wp_t) return hipSuccess;
-    const int CO_f = split_cop(Cout), CO_t = split_cop(Cin);
-    const int nchunks_f = (Cin + SKC - 1) / SKC, nchunks_t = (Cout + SKC - 1) / SKC;
-    const int64_t n_f = wp_f ? packed_split_elems(Cin, Cout, 2) : 0, n_t = wp_t ? packed_split_elems(Cout, Cin, 2) : 0;
+    int64_t en[16];
+    (void)pack_entry<PackSplit<2>>(Cin, Cout, en);
+    const int64_t n_f = wp_f ? en[8] : 0, n_t = wp_t ? en[12] : 0;
     float* word = wp_f ? wp_f + (F16_HDR_ELEMS + n_f) / 2 : wp_t + (F16_HDR_ELEMS + n_t) / 2;
     hipError_t e = hipMemsetAsync(word, 0, AMAX_SLOTS * sizeof(float), s);
     if (e != hipSuccess) return e;
     e = launch_amax(w, (int64_t)Cin * Cout * 9, word, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(pack_weights_3x3_split_f16_both, dim3(grid_1d_s(n_f + n_t, 256)), dim3(256), 0, s, w, reinterpret_cast<__bf16*>(wp_f),
-                       reinterpret_cast<__bf16*>(wp_t), word, Cin, Cout, CO_f, nchunks_f, n_f, CO_t, nchunks_t, n_t);
-    return hipGetLastError();
+    return launch_kernel<pack_weights_3x3_split_f16_both>(dim3(grid_1d(n_f + n_t, 256)), dim3(256), 0, s, w, reinterpret_cast<__bf16*>(wp_f),
+                                                          reinterpret_cast<__bf16*>(wp_t), (const float*)word, Cin, Cout, (int)en[5], (int)en[6],
+                                                          n_f, (int)en[9], (int)en[10], n_t);
 }
 
 int64_t pack_group_entry_split_f16(int Cin, int Cout, int64_t* out)
@@ -1307,15 +1252,13 @@ hipError_t launch_conv3x3_split_mfma(const float* in, const float* w, const floa
             if (e != hipSuccess) return e;
             e = launch_amax(w, (int64_t)Cin * Cout * 9, w_word, s);
             if (e != hipSuccess) return e;
-            e = launch_kernel<pack_weights_3x3_split_f16>(dim3(grid_1d_s(pelems, 256)), dim3(256), 0, s, w, wp, w_word, Cin, Cout, COP, nchunks,
+            e = launch_kernel<pack_weights_3x3_split_f16>(dim3(grid_1d(pelems, 256)), dim3(256), 0, s, w, wp, w_word, Cin, Cout, COP, nchunks,
                                                           pelems, w_transposed_flipped);
             if (e != hipSuccess) return e;
         }
     } else if (!prepacked) {
-        e = with_flags([&](auto p3) {
-            return launch_kernel<pack_weights_3x3_split_both<p3() ? 3 : 2>>(dim3(grid_1d_s(welems, 256)), dim3(256), 0, s, w, wp, (__bf16*)nullptr, Cin,
-                                                                            Cout, COP, nchunks, welems, 0, 0, (int64_t)0, w_transposed_flipped);
-        }, pieces == 3);
+        e = pieces == 3 ? launch_pack_pair<PackSplit<3>>(w, workspace, nullptr, Cin, Cout, w_transposed_flipped != 0, s)
+                        : launch_pack_pair<PackSplit<2>>(w, workspace, nullptr, Cin, Cout, w_transposed_flipped != 0, s);
         if (e != hipSuccess) return e;
     }
     // dispatch.  One argument list for every instance: a launch split over K leaves the mask and the output's bound to its slice-sum
@@ -1353,7 +1296,7 @@ hipError_t launch_conv3x3_split_mfma(const float* in, const float* w, const floa
     }, p.CO == 64, pieces == 3, f16, p.vec, p.masked, p.w16, p.tail, walk > 0, p.ct);
     if (e != hipSuccess || p.ksplit == 1) return e;
     // epilogue: the slice sum
-    return launch_kernel<conv3x3_split_splitk_epilogue>(dim3(grid_1d_s((int64_t)N * Cout * H * W, 256)), dim3(256), 0, s, slab, bias, scale, shift,
+    return launch_kernel<conv3x3_split_splitk_epilogue>(dim3(grid_1d((int64_t)N * Cout * H * W, 256)), dim3(256), 0, s, slab, bias, scale, shift,
                                                         out, (int64_t)N * Cout * H * W, (int64_t)H * W, Cout, p.ksplit, act, slope, ex.residual,
                                                         ex.res_scale, ex.out_mask, ex.out_amax);
 }

@@ -25,12 +25,12 @@
 #include <stdlib.h>
 
 #include "conv_kernels.h"
+#include "conv_device.h"
 #include "conv_launch.h"
+#include "conv_pack.h"
 
 namespace sstem {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
@@ -39,21 +39,7 @@ constexpr int KC = 8;                 // channels of the reduction per K chunk
 constexpr int KK = KC * 9;            // 72 k-values per chunk
 constexpr int TH = 8, TW = 32;        // tile in INPUT pixels (forward) / gradient-input pixels (dgrad)
 constexpr int CO = 32;                // output channels per workgroup
-
-__device__ __forceinline__ float act_apply(float v, int act, float slope)
-{
-    if (act == 1) return v > 0.f ? v : 0.f;
-    if (act == 2) return v > 0.f ? v : v * slope;
-    return v;
-}
-
-inline int grid_1d(int64_t n, int threads)
-{
-    int64_t g = (n + threads - 1) / threads;
-    if (g > 256 * 32) g = 256 * 32;
-    if (g < 1) g = 1;
-    return (int)g;
-}
+static_assert(KC == PACK_F32_KC && KK == PACK_F32_KK, "pack_f32_slot decodes these kernels' K chunk");
 
 // ---- weight packing (same layout as conv_kernels.hip: Wp[cb][chunk][k'][32], k' = (cl%4)*9 + tap + 36*(cl/4)) ------------
 // W is the ConvTranspose weight [Cin][Cout][3][3].
@@ -64,14 +50,8 @@ __global__ void convT_pack_weights(const float* __restrict__ w, float* __restric
 {
     const int64_t total = (int64_t)ncb * nchunks * KK * CO;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-        const int col = idx % CO;
-        int64_t r = idx / CO;
-        const int kp = r % KK; r /= KK;
-        const int chunk = r % nchunks;
-        const int cb = r / nchunks;
-        const int half = kp / 36, rem = kp % 36;
-        const int cl = rem / 9 + 4 * half, tap = rem % 9;
-        const int kch = chunk * KC + cl, row = cb * CO + col;
+        const PackF32Slot k = pack_f32_slot(idx, CO, nchunks);
+        const int kch = k.ci, row = k.co, tap = k.tap;
         float v = 0.f;
         if (rows_are_cout) { if (kch < Cin && row < Cout) v = w[((int64_t)kch * Cout + row) * 9 + tap]; }
         else               { if (kch < Cout && row < Cin) v = w[((int64_t)row * Cout + kch) * 9 + tap]; }
