@@ -13,9 +13,20 @@
 
 namespace sstem {
 
+// a * b rounded to float32, whatever consumes it.  __fmul_rn does NOT say that here: the compiler's header defines it as plain ``a * b``, and
+// under hipcc's default -ffp-contract=fast-honor-pragmas the product was fused into a following subtraction: the 4-per-thread up-sampling
+// kernel formed the weights of two of its four columns as fma(rx, ox, -x0), from the UNROUNDED coordinate (up to 6.3 units of 2^-24 S from
+// the float64 reference at W = 6, where 4 is the arithmetic's own bound).  The pragma is the one that default honours: the multiply carries
+// no contract flag, so no pass may fuse it.
+__device__ __forceinline__ float mul_rn(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a * b;
+}
+
 // w0 a + w1 b with the rounding spelled out (one multiply, one fma): the three forward kernels below share it, so WHICH of them a plane's
 // size selects does not change a bit of the result (left to the compiler's contraction they differed by one ulp on ~8 % of the outputs)
-__device__ __forceinline__ float lerp2(float w0, float a, float w1, float b) { return __fmaf_rn(w1, b, __fmul_rn(w0, a)); }
+__device__ __forceinline__ float lerp2(float w0, float a, float w1, float b) { return __fmaf_rn(w1, b, mul_rn(w0, a)); }
 
 // ---- bilinear x2 up-sampling, align_corners = True ------------------------------------------------
 // nn.Upsample(scale_factor=2, mode='bilinear', align_corners=True): sff_scripts_interp/model/model_interp.py:17,
@@ -40,19 +51,19 @@ __global__ __launch_bounds__(256) void upsample_bilinear2x_ac(const float* __res
     const uint32_t oy = e / q_per_row, q = e - oy * q_per_row;
     // source coordinates: ROUNDED products (torch rounds src = scale * dst before taking the fraction; letting the compiler
     // fuse the multiply into the subtraction below moves the weight by ~1 ulp of the coordinate, 4e-6 at x = 31)
-    const float sy = __fmul_rn(ry, (float)oy);
+    const float sy = mul_rn(ry, (float)oy);
     const int y0 = (int)sy;
     const int ystep = (y0 < H - 1) ? 1 : 0;
     const float l1y = sy - (float)y0, l0y = 1.f - l1y;
     const uint32_t ox = q * 4u;
-    const int xlo = (int)__fmul_rn(rx, (float)ox);      // first source column of the four outputs
+    const int xlo = (int)mul_rn(rx, (float)ox);      // first source column of the four outputs
     int xs[4];
     float l1x[4];
     int d0[4], d1[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         xs[k] = (xlo + k < W) ? xlo + k : W - 1;
-        const float sx = __fmul_rn(rx, (float)(ox + k));
+        const float sx = mul_rn(rx, (float)(ox + k));
         const int x0 = (int)sx;
         l1x[k] = sx - (float)x0;
         d0[k] = x0 - xlo;                               // 0..2: four outputs span at most two source pixels + one
@@ -132,9 +143,9 @@ __global__ __launch_bounds__(256) void upsample_bilinear2x_ac_tiled(const float*
     const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
     const int X0 = tx * UT_COLS, Y0 = ty * UT_ROWS;
     const int ox = X0 + threadIdx.x;
-    const int xs_lo = (int)__fmul_rn(rx, (float)X0), ys_lo = (int)__fmul_rn(ry, (float)Y0);
+    const int xs_lo = (int)mul_rn(rx, (float)X0), ys_lo = (int)mul_rn(ry, (float)Y0);
     // this thread's column
-    const float sx = __fmul_rn(rx, (float)(ox < OW ? ox : OW - 1));
+    const float sx = mul_rn(rx, (float)(ox < OW ? ox : OW - 1));
     const int x0 = (int)sx;
     const float l1x = sx - (float)x0, l0x = 1.f - l1x;
     const int c0 = x0 - xs_lo;                                   // 0 .. 129; c0 + 1 is staged too (clamped to W - 1)
@@ -144,7 +155,7 @@ __global__ __launch_bounds__(256) void upsample_bilinear2x_ac_tiled(const float*
 #pragma unroll
     for (int i = 0; i < UT_ROWS; ++i) {
         const int oy = Y0 + i < OH ? Y0 + i : OH - 1;
-        const float sy = __fmul_rn(ry, (float)oy);
+        const float sy = mul_rn(ry, (float)oy);
         const int y0 = (int)sy;
         l1y[i] = sy - (float)y0; l0y[i] = 1.f - l1y[i];
         r0[i] = y0 - ys_lo;                                      // 0 .. 2; row r0 + 1 is staged too (clamped to H - 1)
@@ -207,12 +218,12 @@ __global__ __launch_bounds__(256) void upsample_bilinear2x_ac_wide(const float* 
     const int bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
     const int X0 = bx * COLS, Y0 = by * ROWS;
     const int tx = threadIdx.x % TXL, ty = threadIdx.x / TXL;
-    const int xs_lo = (int)__fmul_rn(rx, (float)X0), ys_lo = (int)__fmul_rn(ry, (float)Y0);
+    const int xs_lo = (int)mul_rn(rx, (float)X0), ys_lo = (int)mul_rn(ry, (float)Y0);
     int c0[4]; float l0x[4], l1x[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int ox = X0 + 4 * tx + k;
-        const float sx = __fmul_rn(rx, (float)(ox < OW ? ox : OW - 1));
+        const float sx = mul_rn(rx, (float)(ox < OW ? ox : OW - 1));
         const int x0 = (int)sx;
         l1x[k] = sx - (float)x0; l0x[k] = 1.f - l1x[k];
         c0[k] = x0 - xs_lo;
@@ -221,7 +232,7 @@ __global__ __launch_bounds__(256) void upsample_bilinear2x_ac_wide(const float* 
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int oy = Y0 + 4 * ty + i < OH ? Y0 + 4 * ty + i : OH - 1;
-        const float sy = __fmul_rn(ry, (float)oy);
+        const float sy = mul_rn(ry, (float)oy);
         const int y0 = (int)sy;
         l1y[i] = sy - (float)y0; l0y[i] = 1.f - l1y[i];
         r0[i] = y0 - ys_lo;                                        // row r0 + 1 is staged too (clamped to H - 1)
@@ -350,7 +361,7 @@ __global__ __launch_bounds__(256) void upsample_bilinear2x_ac_backward(const flo
         const int oy = 2 * y - 2 + k;
         float w = 0.f;
         if (oy >= 0 && oy < OH) {
-            const float sy = __fmul_rn(ry, (float)oy);
+            const float sy = mul_rn(ry, (float)oy);
             const int y0 = (int)sy;
             const float l1 = sy - (float)y0, l0 = 1.f - l1;
             const int y1 = y0 + ((y0 < H - 1) ? 1 : 0);
@@ -360,7 +371,7 @@ __global__ __launch_bounds__(256) void upsample_bilinear2x_ac_backward(const flo
         const int ox = 2 * x - 2 + k;
         float v = 0.f;
         if (ox >= 0 && ox < OW) {
-            const float sx = __fmul_rn(rx, (float)ox);
+            const float sx = mul_rn(rx, (float)ox);
             const int x0 = (int)sx;
             const float l1 = sx - (float)x0, l0 = 1.f - l1;
             const int x1 = x0 + ((x0 < W - 1) ? 1 : 0);
@@ -520,7 +531,7 @@ __global__ __launch_bounds__(256) void f32_to_gray_u8(const float* __restrict__ 
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
         float p = pred[i];
         if (clamp01) p = p > 1.f ? 1.f : (p < 0.f ? 0.f : p);          // TrainTensor2mask, gray2tensor.py:26-31
-        const float v = __fmul_rn(p, 255.0f);
+        const float v = mul_rn(p, 255.0f);
         // numpy's float -> uint8 astype on x86-64: truncate toward zero to a wide integer, keep the low 8 bits
         // (no clamp: 256.0 -> 0, -1.0 -> 255); NaN and |v| >= 2^63 -> 0
         long long w = 0;
