@@ -13,6 +13,7 @@ gradient is the same MFMA kernel with transposed+flipped weights, the weight gra
 reduction kernel, the bias gradient a sum.  CPU tensors raise NotImplementedError: there is no
 fallback path.
 """
+import contextlib
 import ctypes
 import os
 
@@ -82,15 +83,7 @@ def _ptr(t):
 
 
 # ---- host-side cost per launch (the eager 2-sample training step is host-bound: ~280 launches at ~18 us of Python each) ----------
-class _NullCtx(object):
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-
-_NULL_CTX = _NullCtx()
+_NULL_CTX = contextlib.nullcontext()
 
 
 def _on(device):
@@ -121,6 +114,17 @@ def _check(t, name):
     if c is not t:                       # a copy of a view (a channel slice of a concatenation's gradient): the bound travels with it
         hand_on_amax(t, c)
     return c
+
+
+def _check_forward_args(x, w, b, scale, shift, recording=False, residual=None, out_refusal=None):
+    """The head of the forward functions: what a recorded launch refuses (out_refusal: why this call may not store into `out=`, or
+    None), then _check on everything the launch reads through data_ptr()."""
+    if residual is not None and recording:
+        raise NotImplementedError("a fused residual has no backward (hipnn.fused only fuses it when nothing is recorded)")
+    if out_refusal:
+        raise NotImplementedError(out_refusal)
+    return (_check(x, "input"), _check(w, "weight"), _check(b, "bias") if b is not None else None,
+            _check(scale, "scale") if scale is not None else None, _check(shift, "shift") if shift is not None else None)
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -157,25 +161,21 @@ def conv3x3_bf16io(x, w, b=None, scale=None, shift=None, act=ACT_NONE, slope=0.0
     else:           # the caller's tensor (run_fused(out=...))
         assert tuple(out.shape) == (N, Cout, H, W) and out.dtype == (torch.bfloat16 if out_bf16 else torch.float32) \
             and out.device == x.device and out.is_contiguous()
-    ws_n = _q("sstem_conv3x3_forward_workspace_floats_algo", N, Cin, H, W, Cout, ALGO_MFMA_BF16)
-    prepacked = False
     if prepacked_ws is not None:                  # a workspace whose head already holds this call's packed weights
-        ws, prepacked = prepacked_ws, True
-        ws_n = ws.numel()
-    elif owner is not None:
-        ws, prepacked = _cached_workspace(owner, w, (False, ALGO_MFMA_BF16, N, Cin, H, W, Cout), ws_n, w)
+        ws, ws_n, prepacked = prepacked_ws, prepacked_ws.numel(), True
     else:
-        ws = w.new_empty((max(ws_n, 1),))
+        ws, ws_n, prepacked = _workspace(w, "sstem_conv3x3_forward_workspace_floats_algo", N, Cin, H, W, Cout, ALGO_MFMA_BF16,
+                                         owner=owner, w=w, key=(False, ALGO_MFMA_BF16, N, Cin, H, W, Cout))
     with _on(x.device):
         if in_mask is not None or out_mask is not None:      # the ReLU mask written / applied by the launch (see _MASK_FUSION)
             rc = lib.sstem_conv3x3_forward_bf16io_masked(x.data_ptr(), 1 if x.dtype == torch.bfloat16 else 0, _ptr(in_mask), w.data_ptr(),
                                                          _ptr(b), _ptr(scale), _ptr(shift), out.data_ptr(), 1 if out_bf16 else 0,
                                                          _ptr(out_mask), ws.data_ptr(), ws_n, N, Cin, H, W, Cout,
-                                                         2 if prepacked else 0, act, float(slope), _stream())
+                                                         _flags(False, prepacked), act, float(slope), _stream())
         else:
             rc = lib.sstem_conv3x3_forward_bf16io(x.data_ptr(), 1 if x.dtype == torch.bfloat16 else 0, w.data_ptr(), _ptr(b), _ptr(scale),
                                                   _ptr(shift), out.data_ptr(), 1 if out_bf16 else 0, ws.data_ptr(), ws_n, N, Cin, H, W, Cout,
-                                                  2 if prepacked else 0, act, float(slope), _stream())
+                                                  _flags(False, prepacked), act, float(slope), _stream())
     sstem_native.check(rc, "sstem_conv3x3_forward_bf16io")
     return out
 
@@ -303,6 +303,21 @@ def _cached_workspace(owner, w, key, ws_n, like):
         store.pop(next(iter(store)))                      # oldest entry
     store[key] = (sig, ws)
     return ws, False
+
+
+def _workspace(like, query, *args, owner=None, w=None, key=None):
+    """The workspace of one launch: as many floats as the size query ``query(*args)`` answers, on `like`'s device; with an `owner`,
+    the tensor its cache keeps under `key` for the weights `w` (_cached_workspace).  Returns (workspace, floats, prepacked)."""
+    ws_n = _q(query, *args)
+    if owner is not None:
+        ws, prepacked = _cached_workspace(owner, w, key, ws_n, like)
+        return ws, ws_n, prepacked
+    return like.new_empty((max(ws_n, 1),)), ws_n, False
+
+
+def _flags(transposed, prepacked):
+    """The flag word of the forward entry points (include/sstem_conv.h, SSTEM_CONV_WEIGHT_TRANSPOSED | SSTEM_CONV_WEIGHT_PREPACKED)."""
+    return (1 if transposed else 0) | (2 if prepacked else 0)
 
 
 _bf16_fallback_logged = set()
@@ -434,6 +449,20 @@ def _mask_fusable(algo, W):
     return algo in _SPLIT_ALGOS or (algo in (ALGO_MFMA_BF16, ALGO_MFMA_F16X3) and W % 4 == 0)
 
 
+def _scaled_unsplit_algo(N, Cin, H, W, Cout):
+    """The id a 3x3 launch nothing is recorded for runs under, when it goes through the scaled entry and the NCHW launch would not be
+    split over K (a blocked, strided or pooled store never is: the two spellings must give the same bits); None otherwise."""
+    algo = _forced_algo
+    if algo == ALGO_AUTO:
+        algo = _inference_algo(N, Cin, H, W, Cout)
+    algo = _layer_algo(N, Cin, H, W, Cout, algo)
+    if not (algo == ALGO_MFMA_F16X3 or (algo in _SPLIT_ALGOS and _AUTO_F16)):
+        return None
+    if _q("sstem_conv3x3_forward_workspace_floats_algo", N, Cin, H, W, Cout, algo) != _q("sstem_conv3x3_packed_floats", Cin, Cout, algo):
+        return None
+    return algo
+
+
 def blocked_store_ok(x, conv):
     """Can the launch of the 3x3 `conv` on x store its output in the row-segment layout [N, H, ceil(W/64), Cout, 64] the sepconv
     apply reads (include/sstem_conv.h, SSTEM_LAYOUT_ROW_SEGMENTS)?  Nothing recorded for a backward, a launch that runs under a
@@ -444,15 +473,7 @@ def blocked_store_ok(x, conv):
         return False
     N, Cin, H, W = x.shape
     Cout = conv.weight.shape[0]
-    algo = _forced_algo
-    if algo == ALGO_AUTO:
-        algo = _inference_algo(N, Cin, H, W, Cout)
-    algo = _layer_algo(N, Cin, H, W, Cout, algo)
-    scaled_entry = algo == ALGO_MFMA_F16X3 or (algo in _SPLIT_ALGOS and _AUTO_F16)
-    if not scaled_entry or H * ((W + 63) // 64) * Cout * 256 >= (1 << 32):
-        return False
-    # ... and one the NCHW launch would not split over K either (a blocked store never is: the two spellings must give the same bits)
-    return _q("sstem_conv3x3_forward_workspace_floats_algo", N, Cin, H, W, Cout, algo) == _q("sstem_conv3x3_packed_floats", Cin, Cout, algo)
+    return H * ((W + 63) // 64) * Cout * 256 < (1 << 32) and _scaled_unsplit_algo(N, Cin, H, W, Cout) is not None
 
 
 LAYOUT_NCHW, LAYOUT_ROW_SEGMENTS, LAYOUT_CONVT_PARITY = 0, 1, 2        # include/sstem_conv.h, SSTEM_LAYOUT_*
@@ -463,11 +484,8 @@ def _channel_block_stride(out):
     else is a caller's error."""
     if out.is_contiguous():
         return 0
-    N, C, H, W = out.shape
-    st = out.stride()
-    assert st[1] == H * W and st[2] == W and st[3] == 1 and st[0] >= C * H * W and out.data_ptr() % 16 == 0, \
-        "out= must be contiguous or a channel block of a contiguous NCHW tensor"
-    return st[0]
+    assert is_channel_block(out), "out= must be contiguous or a channel block of a contiguous NCHW tensor"
+    return out.stride(0)
 
 
 def is_channel_block(out):
@@ -494,12 +512,7 @@ def pooled_store_ok(x, conv, pool):
     Cout = conv.weight.shape[0]
     if H % 8 or W % 32 or Cout * H * W * 4 >= (1 << 32):
         return 0
-    algo = _forced_algo
-    if algo == ALGO_AUTO:
-        algo = _inference_algo(N, Cin, H, W, Cout)
-    if _layer_algo(N, Cin, H, W, Cout, algo) != ALGO_MFMA_F16X3:
-        return 0
-    if _q("sstem_conv3x3_forward_workspace_floats_algo", N, Cin, H, W, Cout, algo) != _q("sstem_conv3x3_packed_floats", Cin, Cout, algo):
+    if _scaled_unsplit_algo(N, Cin, H, W, Cout) != ALGO_MFMA_F16X3:
         return 0
     return POOL_MAX if kind == "max" else POOL_AVG
 
@@ -522,23 +535,96 @@ def strided_store_ok(x, conv, out):
         return False
     N, Cin, H, W = x.shape
     Cout = conv.weight.shape[0]
+    return _scaled_unsplit_algo(N, Cin, H, W, Cout) is not None
+
+
+ENTRY_SCALED_MASKED, ENTRY_MASKED_BF16, ENTRY_MASKED_F32, ENTRY_SCALED_STRIDED, ENTRY_EX = range(5)     # the forward entry a call reaches
+
+
+def _conv_plan(N, Cin, H, W, Cout, KH, KW, transposed, inference, prepacked_algo, has_bn_part, masked, has_residual, out_blocked,
+               out_stride, pooled):
+    """Which id and which entry point a _raw_conv call reaches: (algo, stream_small, entry).  Decisions only -- no launch, no
+    allocation, no workspace lookup (_q asks the library size / support questions).  prepacked_algo: the id of the caller's packed
+    workspace, or None; masked: an input or an output mask is given; pooled: a pooled copy is asked for."""
     algo = _forced_algo
-    if algo == ALGO_AUTO:
-        algo = _inference_algo(N, Cin, H, W, Cout)
-    algo = _layer_algo(N, Cin, H, W, Cout, algo)
-    if not (algo == ALGO_MFMA_F16X3 or (algo in _SPLIT_ALGOS and _AUTO_F16)):
-        return False
-    return _q("sstem_conv3x3_forward_workspace_floats_algo", N, Cin, H, W, Cout, algo) == _q("sstem_conv3x3_packed_floats", Cin, Cout, algo)
+    # the fp16 two-piece id serves launches nothing is recorded for (`inference`: the caller says so by naming the owner, or by asking
+    # for it) that need none of the training extras; everything else of a forced fp16 id runs under X6
+    f16_ok = inference and not transposed and prepacked_algo is None and not has_bn_part and not masked
+    if algo == ALGO_MFMA_F16X3 and not f16_ok:
+        algo = ALGO_MFMA_BF16X6
+    if algo in (ALGO_MFMA, ALGO_MFMA_BF16, ALGO_MFMA_F16X3) + _SPLIT_ALGOS and (KH, KW) != (3, 3):
+        algo = ALGO_DIRECT
+    if (KH, KW) == (3, 3):
+        if algo == ALGO_AUTO and prepacked_algo is None:
+            algo = ALGO_MFMA if has_bn_part else (_inference_algo(N, Cin, H, W, Cout) if f16_ok else _auto_algo(N, Cin, H, W, Cout))
+        algo = _layer_algo(N, Cin, H, W, Cout, algo)
+    # decided BEFORE the workspace lookup: the streaming kernel reads the plain weights and packs nothing, so it must not register a
+    # workspace under this call's key either (a later launch of the same module that takes the packed path -- a residual, a strided or
+    # pooled store, a forced id -- would find the entry, believe it packed and multiply uninitialised memory: round-4 advisor finding)
+    stream_small = (KH, KW) == (3, 3) and f16_ok and _forced_algo == ALGO_AUTO and not has_residual and not out_blocked \
+        and out_stride == 0 and not pooled and _stream_small_ok(N, Cin, H, W, Cout)
+    if prepacked_algo is not None:               # the id the caller's workspace was packed under
+        algo = prepacked_algo
+    if (KH, KW) == (3, 3) and algo == ALGO_MFMA_F16X3 and (masked or not inference):
+        # a recorded launch on fp16 pieces (the pair workspace holds the packed weights behind their bound): masks inside, bound left behind
+        entry = ENTRY_SCALED_MASKED
+    elif masked:
+        entry = ENTRY_MASKED_BF16 if algo == ALGO_MFMA_BF16 else ENTRY_MASKED_F32
+    elif stream_small or ((KH, KW) == (3, 3) and inference and (algo == ALGO_MFMA_F16X3 or (algo in _SPLIT_ALGOS and _AUTO_F16 and not has_bn_part))):
+        # the scaled entry: the fp16 id needs the input's bound; every split launch of an inference chain leaves its output's bound
+        # behind for the next layer (the largest value it stores), so only tensors from other producers are ever measured
+        entry = ENTRY_SCALED_STRIDED
+    else:
+        entry = ENTRY_EX
+    return algo, stream_small, entry
+
+
+def _launch_scaled_strided(x, w, b, scale, shift, residual, res_scale, out, ws, ws_n, dims, flags, act, slope, algo, layout, out_stride,
+                           pool_out, pool_kind, what=""):
+    """sstem_conv3x3_forward_scaled_strided_f32; returns the amax word the launch leaves the output's bound in."""
+    in_word = measured_amax_word(x) if algo == ALGO_MFMA_F16X3 else None
+    out_word = _new_amax_word(x.device)
+    with _on(x.device):
+        rc = sstem_native.load_library().sstem_conv3x3_forward_scaled_strided_f32(
+            x.data_ptr(), _ptr(in_word), w.data_ptr(), _ptr(b), _ptr(scale), _ptr(shift), _ptr(residual), float(res_scale),
+            _ptr(out), out_word.data_ptr(), _ptr(ws), ws_n, *dims, flags, act, float(slope), _stream(), algo, layout, out_stride,
+            _ptr(pool_out), int(pool_kind) if pool_out is not None else 0)
+    sstem_native.check(rc, "sstem_conv3x3_forward_scaled_strided_f32" + what)
+    return out_word
+
+
+def _launch_scaled_masked(x, w, b, scale, shift, out, ws, ws_n, dims, flags, act, slope, in_mask, out_mask):
+    in_word = measured_amax_word(x)
+    out_word = _new_amax_word(x.device)
+    with _on(x.device):
+        rc = sstem_native.load_library().sstem_conv3x3_forward_scaled_masked_f32(
+            x.data_ptr(), in_word.data_ptr(), _ptr(in_mask), w.data_ptr(), _ptr(b), _ptr(scale), _ptr(shift), out.data_ptr(),
+            out_word.data_ptr(), _ptr(out_mask), _ptr(ws), ws_n, *dims, flags, act, float(slope), _stream())
+    sstem_native.check(rc, "sstem_conv3x3_forward_scaled_masked_f32")
+    return out_word
+
+
+def _launch_masked(entry, x, w, b, scale, shift, out, ws, ws_n, dims, flags, act, slope, in_mask, out_mask, algo):
+    lib = sstem_native.load_library()
+    with _on(x.device):
+        if entry == ENTRY_MASKED_BF16:
+            rc = lib.sstem_conv3x3_forward_bf16io_masked(
+                x.data_ptr(), 0, _ptr(in_mask), w.data_ptr(), _ptr(b), _ptr(scale), _ptr(shift), out.data_ptr(), 0, _ptr(out_mask),
+                _ptr(ws), ws_n, *dims, flags, act, float(slope), _stream())
+        else:
+            rc = lib.sstem_conv3x3_forward_masked_f32(
+                x.data_ptr(), _ptr(in_mask), w.data_ptr(), _ptr(b), _ptr(scale), _ptr(shift), out.data_ptr(), _ptr(out_mask),
+                _ptr(ws), ws_n, *dims, flags, act, float(slope), _stream(), algo)
+    sstem_native.check(rc, "sstem_conv3x3_forward_masked_f32")
 
 
 def _raw_conv(x, w, b, scale, shift, act, slope, transposed=False, owner=None, prepacked_ws=None, residual=None, res_scale=1.0,
-              bn_part=None, in_mask=None, out_mask=None, out=None, inference=None, out_blocked=False, convt_parity=False, pool_out=None,
-              pool_kind=0, pool_only=False):
+              bn_part=None, in_mask=None, out_mask=None, out=None, inference=None, out_blocked=False, pool_out=None, pool_kind=0,
+              pool_only=False):
     """One native launch; w is [Cout,Cin,KH,KW], or [Cin,Cout,3,3] when transposed.  owner: the module that owns w, given only
     when no backward can follow this call (then the packed weights are cached on it).  residual: out = (act(..) + residual) *
     res_scale in the store; bn_part: a [Cout, P, 3] tensor the launch fills with train-mode BatchNorm statistics partials
-    (include/sstem_conv.h, sstem_conv2d_forward_ex_f32)."""
-    lib = sstem_native.load_library()
+    (include/sstem_conv.h, sstem_conv2d_forward_ex_f32).  Shapes, output tensor, plan (_conv_plan), workspace, launch."""
     if inference is None:
         inference = owner is not None
     N, Cin, H, W = x.shape
@@ -548,29 +634,6 @@ def _raw_conv(x, w, b, scale, shift, act, slope, transposed=False, owner=None, p
     else:
         assert w.shape[1] == Cin, "weight/in-channel mismatch %s vs %s" % (tuple(w.shape), tuple(x.shape))
         Cout, KH, KW = w.shape[0], w.shape[2], w.shape[3]
-    if convt_parity:      # the sub-pixel form of a ConvTranspose2d(k3, s2, p1, op1): w is [4 C, Cin, 3, 3] (convT_subpixel), the store shuffles
-        assert not transposed and (KH, KW) == (3, 3) and Cout % 128 == 0 and prepacked_ws is None and bn_part is None
-        assert in_mask is None and out_mask is None and not out_blocked
-        out_stride = 0
-        if out is None:
-            out = x.new_empty((N, Cout // 4, 2 * H, 2 * W))
-        else:
-            assert tuple(out.shape) == (N, Cout // 4, 2 * H, 2 * W) and out.dtype == torch.float32 and out.device == x.device
-            out_stride = _channel_block_stride(out)
-        ws_n = _q("sstem_conv3x3_forward_workspace_floats_algo", N, Cin, H, W, Cout, ALGO_MFMA_F16X3)
-        if owner is not None:
-            ws, prepacked = _cached_workspace(owner, w, ("convT-subpixel", N, Cin, H, W, Cout), ws_n, x)
-        else:
-            ws, prepacked = x.new_empty((max(ws_n, 1),)), False
-        in_word = measured_amax_word(x)
-        out_word = _new_amax_word(x.device)
-        with _on(x.device):
-            rc = lib.sstem_conv3x3_forward_scaled_strided_f32(
-                x.data_ptr(), in_word.data_ptr(), w.data_ptr(), _ptr(b), _ptr(scale), _ptr(shift), _ptr(residual), float(res_scale),
-                out.data_ptr(), out_word.data_ptr(), ws.data_ptr(), ws_n, N, Cin, H, W, Cout, 2 if prepacked else 0,
-                act, float(slope), _stream(), ALGO_MFMA_F16X3, LAYOUT_CONVT_PARITY, out_stride, None, 0)
-        sstem_native.check(rc, "sstem_conv3x3_forward_scaled_strided_f32 (sub-pixel ConvTranspose)")
-        return tag_amax(out, out_word)
     if out_blocked:       # the caller has asked blocked_store_ok
         assert out is None and residual is None and not transposed and (KH, KW) == (3, 3)
         out = x.new_empty((N, H, (W + 63) // 64, Cout, 64))
@@ -582,86 +645,35 @@ def _raw_conv(x, w, b, scale, shift, act, slope, transposed=False, owner=None, p
         #             storing into the tensor its consumer concatenates; the callers have asked strided_store_ok)
         assert tuple(out.shape) == (N, Cout, H, W) and out.dtype == torch.float32 and out.device == x.device
     out_stride = _channel_block_stride(out) if not (out_blocked or pool_only) else 0
-    algo = _forced_algo
-    # the fp16 two-piece id serves launches nothing is recorded for (`inference`: the caller says so by naming the owner, or by asking
-    # for it) that need none of the training extras; everything else of a forced fp16 id runs under X6
-    f16_ok = inference and not transposed and prepacked_ws is None and bn_part is None and in_mask is None and out_mask is None
-    if algo == ALGO_MFMA_F16X3 and not f16_ok:
-        algo = ALGO_MFMA_BF16X6
-    if algo in (ALGO_MFMA, ALGO_MFMA_BF16, ALGO_MFMA_F16X3) + _SPLIT_ALGOS and (KH, KW) != (3, 3):
-        algo = ALGO_DIRECT
-    if (KH, KW) == (3, 3):
-        if algo == ALGO_AUTO and prepacked_ws is None:
-            algo = ALGO_MFMA if bn_part is not None else (_inference_algo(N, Cin, H, W, Cout) if f16_ok else _auto_algo(N, Cin, H, W, Cout))
-        algo = _layer_algo(N, Cin, H, W, Cout, algo)
-    ws = None
-    ws_n = 0
-    prepacked = False
-    # decided BEFORE the workspace lookup: the streaming kernel reads the plain weights and packs nothing, so it must not register a
-    # workspace under this call's key either (a later launch of the same module that takes the packed path -- a residual, a strided or
-    # pooled store, a forced id -- would find the entry, believe it packed and multiply uninitialised memory: round-4 advisor finding)
-    stream_small = (KH, KW) == (3, 3) and f16_ok and _forced_algo == ALGO_AUTO and residual is None and not out_blocked \
-        and out_stride == 0 and pool_out is None and not pool_only and in_mask is None and out_mask is None \
-        and _stream_small_ok(N, Cin, H, W, Cout)
+    masked = in_mask is not None or out_mask is not None
+    algo, stream_small, entry = _conv_plan(N, Cin, H, W, Cout, KH, KW, transposed, inference, prepacked_ws[0] if prepacked_ws is not None else None,
+                                           bn_part is not None, masked, residual is not None, out_blocked, out_stride,
+                                           pool_out is not None or pool_only)
+    ws, ws_n, prepacked = None, 0, False
     if prepacked_ws is not None:                 # (algo, workspace) whose head already holds this call's packed weights
-        algo, ws = prepacked_ws
+        ws = prepacked_ws[1]
         ws_n, prepacked = ws.numel(), True
-    elif stream_small:
-        pass
-    elif (KH, KW) == (3, 3) and algo != ALGO_DIRECT:
-        ws_n = _q("sstem_conv3x3_forward_workspace_floats_algo", N, Cin, H, W, Cout, algo)   # packed weights + split-K slices
-        if owner is not None:
-            ws, prepacked = _cached_workspace(owner, w, (bool(transposed), algo, N, Cin, H, W, Cout), ws_n, x)
-        else:
-            ws = x.new_empty((max(ws_n, 1),))
+    elif not stream_small and (KH, KW) == (3, 3) and algo != ALGO_DIRECT:      # packed weights + split-K slices
+        ws, ws_n, prepacked = _workspace(x, "sstem_conv3x3_forward_workspace_floats_algo", N, Cin, H, W, Cout, algo,
+                                         owner=owner, w=w, key=(bool(transposed), algo, N, Cin, H, W, Cout))
     if transposed and algo == ALGO_DIRECT:      # the direct kernel wants [Cout,Cin,3,3]
         w = w.transpose(0, 1).flip(2, 3).contiguous()
         transposed = False
-    if (KH, KW) == (3, 3) and algo == ALGO_MFMA_F16X3 and (in_mask is not None or out_mask is not None or not inference):
-        # a recorded launch on fp16 pieces (the pair workspace holds the packed weights behind their bound): masks inside, bound left behind
+    dims, flags = (N, Cin, H, W, Cout), _flags(transposed, prepacked)
+    if entry == ENTRY_SCALED_MASKED:
         assert residual is None and bn_part is None and out_stride == 0 and not out_blocked and pool_out is None
-        assert (in_mask is None and out_mask is None) or _mask_fusable(algo, W)
-        in_word = measured_amax_word(x)
-        out_word = _new_amax_word(x.device)
-        with _on(x.device):
-            rc = lib.sstem_conv3x3_forward_scaled_masked_f32(
-                x.data_ptr(), in_word.data_ptr(), _ptr(in_mask), w.data_ptr(), _ptr(b), _ptr(scale), _ptr(shift), out.data_ptr(),
-                out_word.data_ptr(), _ptr(out_mask), _ptr(ws), ws_n, N, Cin, H, W, Cout, (1 if transposed else 0) | (2 if prepacked else 0),
-                act, float(slope), _stream())
-        sstem_native.check(rc, "sstem_conv3x3_forward_scaled_masked_f32")
-        return tag_amax(out, out_word)
-    if in_mask is not None or out_mask is not None:          # the callers have checked (_mask_fusable): no residual / statistics
+        assert _mask_fusable(algo, W) or not masked
+        return tag_amax(out, _launch_scaled_masked(x, w, b, scale, shift, out, ws, ws_n, dims, flags, act, slope, in_mask, out_mask))
+    if entry in (ENTRY_MASKED_BF16, ENTRY_MASKED_F32):       # the callers have checked (_mask_fusable): no residual / statistics
         assert _mask_fusable(algo, W) and residual is None and bn_part is None
-        with _on(x.device):
-            if algo == ALGO_MFMA_BF16:
-                rc = lib.sstem_conv3x3_forward_bf16io_masked(
-                    x.data_ptr(), 0, _ptr(in_mask), w.data_ptr(), _ptr(b), _ptr(scale), _ptr(shift), out.data_ptr(), 0, _ptr(out_mask),
-                    _ptr(ws), ws_n, N, Cin, H, W, Cout, (1 if transposed else 0) | (2 if prepacked else 0), act, float(slope), _stream())
-            else:
-                rc = lib.sstem_conv3x3_forward_masked_f32(
-                    x.data_ptr(), _ptr(in_mask), w.data_ptr(), _ptr(b), _ptr(scale), _ptr(shift), out.data_ptr(), _ptr(out_mask),
-                    _ptr(ws), ws_n, N, Cin, H, W, Cout, (1 if transposed else 0) | (2 if prepacked else 0), act, float(slope), _stream(), algo)
-        sstem_native.check(rc, "sstem_conv3x3_forward_masked_f32")
+        _launch_masked(entry, x, w, b, scale, shift, out, ws, ws_n, dims, flags, act, slope, in_mask, out_mask, algo)
         return out
     if stream_small:
-        out_word = _new_amax_word(x.device)
-        with _on(x.device):
-            rc = lib.sstem_conv3x3_forward_scaled_strided_f32(
-                x.data_ptr(), None, w.data_ptr(), _ptr(b), _ptr(scale), _ptr(shift), None, 1.0, out.data_ptr(), out_word.data_ptr(), None, 0,
-                N, Cin, H, W, Cout, 0, act, float(slope), _stream(), ALGO_DIRECT, 0, 0, None, 0)
-        sstem_native.check(rc, "sstem_conv3x3_forward_scaled_strided_f32 (streaming kernel)")
-        return tag_amax(out, out_word)
-    if (KH, KW) == (3, 3) and inference and (algo == ALGO_MFMA_F16X3 or (algo in _SPLIT_ALGOS and _AUTO_F16 and bn_part is None)):
-        # the scaled entry: the fp16 id needs the input's bound; every split launch of an inference chain leaves its output's bound
-        # behind for the next layer (the largest value it stores), so only tensors from other producers are ever measured
-        in_word = measured_amax_word(x) if algo == ALGO_MFMA_F16X3 else None
-        out_word = _new_amax_word(x.device)
-        with _on(x.device):
-            rc = lib.sstem_conv3x3_forward_scaled_strided_f32(
-                x.data_ptr(), _ptr(in_word), w.data_ptr(), _ptr(b), _ptr(scale), _ptr(shift), _ptr(residual), float(res_scale),
-                _ptr(out), out_word.data_ptr(), _ptr(ws), ws_n, N, Cin, H, W, Cout, (1 if transposed else 0) | (2 if prepacked else 0),
-                act, float(slope), _stream(), algo, 1 if out_blocked else 0, out_stride, _ptr(pool_out), int(pool_kind) if pool_out is not None else 0)
-        sstem_native.check(rc, "sstem_conv3x3_forward_scaled_strided_f32")
+        return tag_amax(out, _launch_scaled_strided(x, w, b, scale, shift, None, 1.0, out, None, 0, dims, 0, act, slope, ALGO_DIRECT, 0, 0,
+                                                    None, 0, " (streaming kernel)"))
+    if entry == ENTRY_SCALED_STRIDED:
+        out_word = _launch_scaled_strided(x, w, b, scale, shift, residual, res_scale, out, ws, ws_n, dims, flags, act, slope, algo,
+                                          1 if out_blocked else 0, out_stride, pool_out, pool_kind)
         if pool_out is not None:
             tag_amax(pool_out, out_word)             # a maximum / an average of four stored values: the output's bound holds
         if pool_only:
@@ -671,12 +683,30 @@ def _raw_conv(x, w, b, scale, shift, act, slope, transposed=False, owner=None, p
     assert not out_blocked, "a blocked store needs a launch through the scaled entry (blocked_store_ok)"
     assert out_stride == 0, "a strided store needs a launch through the scaled entry (strided_store_ok)"
     with _on(x.device):
-        rc = lib.sstem_conv2d_forward_ex_f32(
+        rc = sstem_native.load_library().sstem_conv2d_forward_ex_f32(
             x.data_ptr(), w.data_ptr(), _ptr(b), _ptr(scale), _ptr(shift), _ptr(residual), float(res_scale), out.data_ptr(), _ptr(bn_part),
-            _ptr(ws), ws_n, N, Cin, H, W, Cout, KH, KW, KH // 2, KW // 2, (1 if transposed else 0) | (2 if prepacked else 0),
-            act, float(slope), _stream(), algo)
+            _ptr(ws), ws_n, *dims, KH, KW, KH // 2, KW // 2, flags, act, float(slope), _stream(), algo)
     sstem_native.check(rc, "sstem_conv2d_forward_ex_f32")
     return out
+
+
+def _raw_convT_subpixel(x, w, b, scale, shift, act, slope, owner, residual, res_scale, out):
+    """The sub-pixel form of a ConvTranspose2d(k3, s2, p1, op1) on the fp16 two-piece id: w is [4 C, Cin, 3, 3] (convT_subpixel_weight),
+    the store shuffles the four parities into [N, C, 2H, 2W] (include/sstem_conv.h, SSTEM_LAYOUT_CONVT_PARITY)."""
+    N, Cin, H, W = x.shape
+    Cout = w.shape[0]
+    assert w.shape[1] == Cin and tuple(w.shape[2:]) == (3, 3) and Cout % 128 == 0
+    out_stride = 0
+    if out is None:
+        out = x.new_empty((N, Cout // 4, 2 * H, 2 * W))
+    else:
+        assert tuple(out.shape) == (N, Cout // 4, 2 * H, 2 * W) and out.dtype == torch.float32 and out.device == x.device
+        out_stride = _channel_block_stride(out)
+    ws, ws_n, prepacked = _workspace(x, "sstem_conv3x3_forward_workspace_floats_algo", N, Cin, H, W, Cout, ALGO_MFMA_F16X3,
+                                     owner=owner, w=w, key=("convT-subpixel", N, Cin, H, W, Cout))
+    out_word = _launch_scaled_strided(x, w, b, scale, shift, residual, res_scale, out, ws, ws_n, (N, Cin, H, W, Cout), _flags(False, prepacked),
+                                      act, slope, ALGO_MFMA_F16X3, LAYOUT_CONVT_PARITY, out_stride, None, 0, " (sub-pixel ConvTranspose)")
+    return tag_amax(out, out_word)
 
 
 def _act_mask(ctx, out, act, *inputs):
@@ -865,6 +895,41 @@ class _on_side_stream:
         return False
 
 
+class _WgradDelivery(object):
+    """Where one layer's weight (+ bias) gradient goes: ``with d.stream(tensors the launch reads): launch(d.gw, d.gb, d.acc)``, then
+    ``gw, gb = d.done(ws)`` for autograd.  gradient sinks: the launch adds into the parameters' .grad buffers (both or neither -- one
+    accumulate flag: a bias gradient that rides along without a bias sink drops the weight sink too); otherwise gw / gb are fresh
+    tensors.  acc: 0 store, 1 add into the sinks, 3 add and leave the reduce to the grouped launch (_defer_wgrad_ok, and the caller's
+    `may_defer`).  stream(): the side stream when the result goes into sinks.  done(): records the deferred job (`ws`: its slabs)
+    or reports the delivery; None for whatever went into a sink."""
+    __slots__ = ("params", "sunk", "gw", "gb", "defer", "acc", "flop")
+
+    def __init__(self, pw, pb, with_bias, w, Cout, g, flop, may_defer=True):
+        sink_w = _grad_sink(pw, True)
+        sink_b = _grad_sink(pb, with_bias) if sink_w is not None else None
+        if with_bias and sink_b is None:
+            sink_w = None
+        self.sunk = sink_w is not None
+        self.params = (pw, pb if with_bias else None)
+        self.gw = sink_w if self.sunk else torch.empty_like(w)
+        self.gb = (sink_b if self.sunk else g.new_empty((Cout,))) if with_bias else None
+        self.defer = self.sunk and may_defer and _defer_wgrad_ok(*self.params, flop=flop)
+        self.acc = 3 if self.defer else (1 if self.sunk else 0)
+        self.flop = flop
+
+    def stream(self, *tensors):
+        return _on_side_stream(self.sunk, *tensors, flop=self.flop)
+
+    def done(self, ws):
+        if not self.sunk:
+            return self.gw, self.gb
+        if self.defer:
+            _deferred_wgrad_issued(ws, *self.params)
+        else:
+            _sink_done(*self.params)
+        return None, None
+
+
 def _mask_grad(g, mask, act, slope):
     # one select kernel per activation (a cast of the mask + a multiply were two, 23 us per fused ReLU of an IFNet step)
     if act == ACT_RELU:
@@ -1047,14 +1112,8 @@ class _Conv2dFused(torch.autograd.Function):
                 out_blocked=False, pool_out=None, pool_kind=0):
         ctx.recording = recording
         ctx.params = (w, b)                      # the Parameter objects themselves (their .grad may be a gradient sink)
-        if residual is not None and recording:
-            raise NotImplementedError("a fused residual has no backward (hipnn.fused only fuses it when nothing is recorded)")
-        if out is not None and recording:
-            raise NotImplementedError("out= is for launches nothing is recorded for (hipnn.fused only passes it then)")
-        x = _check(x, "input"); w = _check(w, "weight")
-        b = _check(b, "bias") if b is not None else None
-        scale = _check(scale, "scale") if scale is not None else None
-        shift = _check(shift, "shift") if shift is not None else None
+        refusal = "out= is for launches nothing is recorded for (hipnn.fused only passes it then)" if (out is not None and recording) else None
+        x, w, b, scale, shift = _check_forward_args(x, w, b, scale, shift, recording, residual, refusal)
         if w.shape[2] != w.shape[3] or w.shape[2] % 2 != 1:
             raise NotImplementedError("only odd square kernels with 'same' padding")
         ctx.dgrad_ws = None
@@ -1079,12 +1138,9 @@ class _Conv2dFused(torch.autograd.Function):
         return out
 
     @staticmethod
-    def backward(ctx, g):
-        x, w, mask = ctx.saved_tensors
-        if ctx.folded:
-            raise NotImplementedError("backward through a folded (eval-mode) BatchNorm affine is not supported")
-        g = _check(g, "grad_output")
-        lib = sstem_native.load_library()
+    def _backward_plan(ctx, x, w, g, mask):
+        """What the backward launches of this layer are: (want_gb, fuse, wg_algo, wg_f16) -- a bias gradient is wanted, the ReLU mask
+        is applied inside the gradient launches, the weight gradient's id, the weight gradient runs on fp16 pieces."""
         N, Cin, H, W = x.shape
         Cout, _, KH, KW = w.shape
         want_gb = ctx.has_bias and ctx.needs_input_grad[2]
@@ -1106,9 +1162,22 @@ class _Conv2dFused(torch.autograd.Function):
             fuse = False
         if fuse and want_gb and not ctx.needs_input_grad[1]:
             fuse = False                         # a bias gradient on its own is a torch reduction of the masked tensor
+        return want_gb, fuse, wg_algo, wg_f16
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, mask = ctx.saved_tensors
+        if ctx.folded:
+            raise NotImplementedError("backward through a folded (eval-mode) BatchNorm affine is not supported")
+        g = _check(g, "grad_output")
+        lib = sstem_native.load_library()
+        N, Cin, H, W = x.shape
+        Cout, _, KH, KW = w.shape
+        want_gb, fuse, wg_algo, wg_f16 = _Conv2dFused._backward_plan(ctx, x, w, g, mask)
         if not fuse:
             g = _mask_grad(g, mask, ctx.act, ctx.slope)
         gx = gw = gb = None
+        fused_gb = False
         if ctx.needs_input_grad[0]:
             if (KH, KW) == (3, 3):
                 gx = _raw_conv(g, w, None, None, None, ACT_NONE, 0.0, transposed=True, prepacked_ws=ctx.dgrad_ws,
@@ -1117,54 +1186,36 @@ class _Conv2dFused(torch.autograd.Function):
                 gx = _raw_conv(g, w.transpose(0, 1).flip(2, 3).contiguous(), None, None, None, ACT_NONE, 0.0)
         if ctx.needs_input_grad[1]:
             algo = ALGO_MFMA_F16X3 if wg_f16 else wg_algo
-            fused_gb = want_gb and (KH, KW) == (3, 3) and algo != ALGO_DIRECT     # the bias gradient rides along with the 3x3 MFMA weight gradient
+            mfma3x3 = (KH, KW) == (3, 3) and algo != ALGO_DIRECT
+            fused_gb = want_gb and mfma3x3           # the bias gradient rides along with the 3x3 MFMA weight gradient
             x_word = g_word = None
             if wg_f16:                               # bounds of both operands, measured on THIS stream where no producer left one
                 x_word = ctx.x_word if (ctx.x_word is not None and amax_word_of(x) is None) else measured_amax_word(x)
                 g_word = measured_amax_word(g)
-            # gradient sinks: the launch adds into the parameters' .grad buffers (both or neither: one accumulate flag)
-            sink_w = _grad_sink(ctx.params[0], True)
-            sink_b = _grad_sink(ctx.params[1], fused_gb) if sink_w is not None else None
-            if fused_gb and sink_b is None:
-                sink_w = None
-            gw = sink_w if sink_w is not None else torch.empty_like(w)
-            if fused_gb:
-                gb = sink_b if sink_b is not None else g.new_empty((Cout,))
-            defer = sink_w is not None and (KH, KW) == (3, 3) and algo != ALGO_DIRECT and \
-                _defer_wgrad_ok(ctx.params[0], ctx.params[1] if fused_gb else None, flop=2.0 * N * H * W * Cin * Cout * KH * KW)
-            acc = 3 if defer else (1 if sink_w is not None else 0)
-            with _on_side_stream(sink_w is not None, x, g, mask if fuse else None, x_word, g_word, flop=2.0 * N * H * W * Cin * Cout * KH * KW):
+            d = _WgradDelivery(ctx.params[0], ctx.params[1], fused_gb, w, Cout, g, 2.0 * N * H * W * Cin * Cout * KH * KW, may_defer=mfma3x3)
+            with d.stream(x, g, mask if fuse else None, x_word, g_word):
                 ws, ws_n = None, 0
-                if (KH, KW) == (3, 3) and algo != ALGO_DIRECT:
-                    ws_n = _q("sstem_conv3x3_wgrad_workspace_floats_algo", N, Cin, H, W, Cout, algo)
-                    ws = x.new_empty((max(ws_n, 1),))
+                if mfma3x3:
+                    ws, ws_n, _ = _workspace(x, "sstem_conv3x3_wgrad_workspace_floats_algo", N, Cin, H, W, Cout, algo)
                 with _on(x.device):
                     if wg_f16:
                         rc = lib.sstem_conv3x3_backward_weight_scaled_masked_f32(
-                            x.data_ptr(), x_word.data_ptr(), g.data_ptr(), g_word.data_ptr(), mask.data_ptr() if fuse else None, gw.data_ptr(),
-                            _ptr(gb), _ptr(ws), ws_n, N, Cin, H, W, Cout, acc, _stream())
+                            x.data_ptr(), x_word.data_ptr(), g.data_ptr(), g_word.data_ptr(), mask.data_ptr() if fuse else None, d.gw.data_ptr(),
+                            _ptr(d.gb), _ptr(ws), ws_n, N, Cin, H, W, Cout, d.acc, _stream())
                     elif fuse and algo == ALGO_MFMA_BF16:
-                        rc = lib.sstem_conv3x3_backward_weight_bf16_masked(x.data_ptr(), 0, g.data_ptr(), mask.data_ptr(), gw.data_ptr(), _ptr(gb),
-                                                                           _ptr(ws), ws_n, N, Cin, H, W, Cout, acc, _stream())
+                        rc = lib.sstem_conv3x3_backward_weight_bf16_masked(x.data_ptr(), 0, g.data_ptr(), mask.data_ptr(), d.gw.data_ptr(), _ptr(d.gb),
+                                                                           _ptr(ws), ws_n, N, Cin, H, W, Cout, d.acc, _stream())
                     elif fuse:
-                        rc = lib.sstem_conv3x3_backward_weight_masked_f32(x.data_ptr(), g.data_ptr(), mask.data_ptr(), gw.data_ptr(), _ptr(gb),
-                                                                          _ptr(ws), ws_n, N, Cin, H, W, Cout, acc, _stream(), algo)
+                        rc = lib.sstem_conv3x3_backward_weight_masked_f32(x.data_ptr(), g.data_ptr(), mask.data_ptr(), d.gw.data_ptr(), _ptr(d.gb),
+                                                                          _ptr(ws), ws_n, N, Cin, H, W, Cout, d.acc, _stream(), algo)
                     else:
-                        rc = lib.sstem_conv2d_backward_weight_bias_ex_f32(x.data_ptr(), g.data_ptr(), gw.data_ptr(), _ptr(gb), _ptr(ws), ws_n,
-                                                                          N, Cin, H, W, Cout, KH, KW, KH // 2, KW // 2, acc, _stream(), algo)
+                        rc = lib.sstem_conv2d_backward_weight_bias_ex_f32(x.data_ptr(), g.data_ptr(), d.gw.data_ptr(), _ptr(d.gb), _ptr(ws), ws_n,
+                                                                          N, Cin, H, W, Cout, KH, KW, KH // 2, KW // 2, d.acc, _stream(), algo)
                 sstem_native.check(rc, "sstem_conv2d_backward_weight_bias_ex_f32")
-            if sink_w is not None:
-                gw = None
-                if defer:
-                    _deferred_wgrad_issued(ws, ctx.params[0], ctx.params[1] if fused_gb else None)
-                else:
-                    _sink_done(ctx.params[0], ctx.params[1] if fused_gb else None)
-                if fused_gb:
-                    gb = None
-                    want_gb = False
-        if want_gb and gb is None:
+            gw, gb = d.done(ws)
+        if want_gb and not fused_gb:                 # no launch it could ride along with: a torch reduction
             gb = g.sum((0, 2, 3))
-        return gx, gw, gb, None, None, None, None, None, None, None, None, None, None, None, None, None
+        return (gx, gw, gb) + (None,) * 13
 
 
 _bf16_wgrad = True
@@ -1209,8 +1260,7 @@ def _wgrad3x3(lib, x, g, Cout, want_bias=False):
     algo = _wgrad_algo(N, Cin, H, W, Cout)
     ws, ws_n, gb = None, 0, None
     if algo != ALGO_DIRECT:
-        ws_n = _q("sstem_conv3x3_wgrad_workspace_floats_algo", N, Cin, H, W, Cout, algo)
-        ws = x.new_empty((max(ws_n, 1),))
+        ws, ws_n, _ = _workspace(x, "sstem_conv3x3_wgrad_workspace_floats_algo", N, Cin, H, W, Cout, algo)
         if want_bias:
             gb = g.new_empty((Cout,))
     with _on(x.device):
@@ -1292,8 +1342,8 @@ def _convT_subpixel(x, w, b, scale, shift, act, slope, owner, residual, res_scal
         ent = st["w"] = ((w._version, w.data_ptr()), convT_subpixel_weight(w.detach()), sub)
     if _touch_log is not None:                        # a captured graph must notice a change of the ORIGINAL weights
         _touch_log.append((w,))
-    return _raw_conv(x, ent[1], _rep4_cached(st, "b", b), _rep4_cached(st, "scale", scale), _rep4_cached(st, "shift", shift), act, slope,
-                     owner=ent[2], residual=residual, res_scale=res_scale, inference=True, convt_parity=True, out=out)
+    return _raw_convT_subpixel(x, ent[1], _rep4_cached(st, "b", b), _rep4_cached(st, "scale", scale), _rep4_cached(st, "shift", shift), act, slope,
+                               ent[2], residual, res_scale, out)
 
 
 class _ConvT3x3s2Fused(torch.autograd.Function):
@@ -1306,14 +1356,10 @@ class _ConvT3x3s2Fused(torch.autograd.Function):
     def forward(ctx, x, w, b, scale, shift, act, slope, recording=True, owner=None, residual=None, res_scale=1.0, bn_part=None, out=None):
         ctx.recording = recording
         ctx.params = (w, b)
-        if residual is not None and recording:
-            raise NotImplementedError("a fused residual has no backward (hipnn.fused only fuses it when nothing is recorded)")
+        refusal = None
         if out is not None and (recording or not _convT_subpixel_ok(x, w, owner, recording, bn_part)):
-            raise NotImplementedError("out= is for sub-pixel ConvTranspose launches nothing is recorded for (hipnn.fused asks strided_store_ok)")
-        x = _check(x, "input"); w = _check(w, "weight")
-        b = _check(b, "bias") if b is not None else None
-        scale = _check(scale, "scale") if scale is not None else None
-        shift = _check(shift, "shift") if shift is not None else None
+            refusal = "out= is for sub-pixel ConvTranspose launches nothing is recorded for (hipnn.fused asks strided_store_ok)"
+        x, w, b, scale, shift = _check_forward_args(x, w, b, scale, shift, recording, residual, refusal)
         lib = sstem_native.load_library()
         N, Cin, H, W = x.shape
         assert w.shape[0] == Cin and tuple(w.shape[2:]) == (3, 3)
@@ -1333,16 +1379,12 @@ class _ConvT3x3s2Fused(torch.autograd.Function):
             out = _convT_subpixel(x, w, b, scale, shift, act, slope, owner, residual, res_scale, out)
         else:
             out = x.new_empty((N, Cout, 2 * H, 2 * W))
-            ws_n = _q("sstem_conv_transpose3x3s2_workspace_floats", N, Cin, H, W, Cout, 0)
-            prepacked = False
-            if owner is not None and not recording:
-                ws, prepacked = _cached_workspace(owner, w, ("convT", N, Cin, H, W, Cout), ws_n, x)
-            else:
-                ws = x.new_empty((max(ws_n, 1),))
+            ws, ws_n, prepacked = _workspace(x, "sstem_conv_transpose3x3s2_workspace_floats", N, Cin, H, W, Cout, 0,
+                                             owner=None if recording else owner, w=w, key=("convT", N, Cin, H, W, Cout))
             with _on(x.device):
                 rc = lib.sstem_conv_transpose3x3s2_forward_ex_f32(x.data_ptr(), w.data_ptr(), _ptr(b), _ptr(scale), _ptr(shift), _ptr(residual),
                                                                   float(res_scale), out.data_ptr(), _ptr(bn_part), ws.data_ptr(), ws_n,
-                                                                  N, Cin, H, W, Cout, 2 if prepacked else 0, act, float(slope), _stream())
+                                                                  N, Cin, H, W, Cout, _flags(False, prepacked), act, float(slope), _stream())
             sstem_native.check(rc, "sstem_conv_transpose3x3s2_forward_ex_f32")
         ctx.act, ctx.slope = act, slope
         ctx.has_bias = b is not None
@@ -1362,6 +1404,7 @@ class _ConvT3x3s2Fused(torch.autograd.Function):
         Cout = w.shape[1]
         gx = gw = gb = None
         want_gb = ctx.has_bias and ctx.needs_input_grad[2]
+        fused_gb = False                 # the bias gradient rides along with the native weight gradient
         if ctx.route == "direct":
             gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
             gw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
@@ -1378,47 +1421,26 @@ class _ConvT3x3s2Fused(torch.autograd.Function):
                 gw, gb = _wgrad3x3(lib, _zero_insert(x), g, Cout, want_gb)      # the bias gradient rides along
                 gw = gw.transpose(0, 1).flip(2, 3).contiguous()
         else:
-            want_gw = ctx.needs_input_grad[1]
             gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-            fused_gb = want_gb and want_gw
-            sink_w = _grad_sink(ctx.params[0], want_gw)
-            sink_b = _grad_sink(ctx.params[1], fused_gb) if sink_w is not None else None
-            if fused_gb and sink_b is None:
-                sink_w = None
-            if want_gw:
-                gw = sink_w if sink_w is not None else torch.empty_like(w)
-                if fused_gb:
-                    gb = sink_b if sink_b is not None else g.new_empty((Cout,))
             if gx is not None:          # data gradient: on the critical path, this stream
-                ws_n = _q("sstem_conv_transpose3x3s2_workspace_floats", N, Cin, H, W, Cout, 1)
-                ws = x.new_empty((max(ws_n, 1),))
+                ws, ws_n, _ = _workspace(x, "sstem_conv_transpose3x3s2_workspace_floats", N, Cin, H, W, Cout, 1)
                 with _on(x.device):
                     rc = lib.sstem_conv_transpose3x3s2_backward_ex_f32(x.data_ptr(), w.data_ptr(), g.data_ptr(), gx.data_ptr(), None, None,
                                                                        ws.data_ptr(), ws_n, N, Cin, H, W, Cout, 0, _stream())
                 sstem_native.check(rc, "sstem_conv_transpose3x3s2_backward_ex_f32")
-            defer = False
-            if want_gw:                 # weight (+ bias) gradient: beside it when it goes into a gradient sink
-                defer = sink_w is not None and _defer_wgrad_ok(ctx.params[0], ctx.params[1] if fused_gb else None, flop=18.0 * N * H * W * Cin * Cout)
-                with _on_side_stream(sink_w is not None, x, g, flop=18.0 * N * H * W * Cin * Cout):
-                    ws_n = _q("sstem_conv_transpose3x3s2_workspace_floats", N, Cin, H, W, Cout, 2)
-                    ws = x.new_empty((max(ws_n, 1),))
+            if ctx.needs_input_grad[1]:  # weight (+ bias) gradient: beside it when it goes into a gradient sink
+                fused_gb = want_gb
+                d = _WgradDelivery(ctx.params[0], ctx.params[1], fused_gb, w, Cout, g, 18.0 * N * H * W * Cin * Cout)
+                with d.stream(x, g):
+                    ws, ws_n, _ = _workspace(x, "sstem_conv_transpose3x3s2_workspace_floats", N, Cin, H, W, Cout, 2)
                     with _on(x.device):
-                        rc = lib.sstem_conv_transpose3x3s2_backward_ex_f32(x.data_ptr(), w.data_ptr(), g.data_ptr(), None, gw.data_ptr(), _ptr(gb),
-                                                                           ws.data_ptr(), ws_n, N, Cin, H, W, Cout,
-                                                                           3 if defer else (1 if sink_w is not None else 0), _stream())
+                        rc = lib.sstem_conv_transpose3x3s2_backward_ex_f32(x.data_ptr(), w.data_ptr(), g.data_ptr(), None, d.gw.data_ptr(), _ptr(d.gb),
+                                                                           ws.data_ptr(), ws_n, N, Cin, H, W, Cout, d.acc, _stream())
                     sstem_native.check(rc, "sstem_conv_transpose3x3s2_backward_ex_f32")
-                if defer:
-                    _deferred_wgrad_issued(ws, ctx.params[0], ctx.params[1] if fused_gb else None)
-            if sink_w is not None:
-                gw = None
-                if not defer:
-                    _sink_done(ctx.params[0], ctx.params[1] if fused_gb else None)
-                if fused_gb:
-                    gb = None
-                    want_gb = False
-        if want_gb and gb is None:
+                gw, gb = d.done(ws)
+        if want_gb and gb is None and not fused_gb:
             gb = g.sum((0, 2, 3))
-        return gx, gw, gb, None, None, None, None, None, None, None, None, None, None
+        return (gx, gw, gb) + (None,) * 10
 
 
 class _ConvChain(torch.autograd.Function):
@@ -1457,18 +1479,9 @@ class _ConvChain(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         lib = sstem_native.load_library()
-        saved = list(ctx.saved_tensors)
+        saved = iter(ctx.saved_tensors)
         K = len(ctx.spec)
-        per = []
-        pos = 0
-        for i in range(K):
-            xin, w = saved[pos], saved[pos + 1]
-            pos += 2
-            mask = None
-            if ctx.has_mask[i]:
-                mask = saved[pos]
-                pos += 1
-            per.append((xin, w, mask))
+        per = [(next(saved), next(saved), next(saved) if has_mask else None) for has_mask in ctx.has_mask]      # (input, weight, mask)
         g = _check(g, "grad_output")
         grads = [None] * (2 * K)
         for i in reversed(range(K)):
@@ -1485,36 +1498,22 @@ class _ConvChain(torch.autograd.Function):
                 g = _mask_grad(g, mask, act, slope)
             if ctx.needs_input_grad[2 + 2 * i]:
                 want_gb = ctx.has_bias[i] and ctx.needs_input_grad[3 + 2 * i]
-                sink_w = _grad_sink(ctx.params[2 * i], True)
-                sink_b = _grad_sink(ctx.params[2 * i + 1], want_gb) if sink_w is not None else None
-                if want_gb and sink_b is None:
-                    sink_w = None
-                gw = sink_w if sink_w is not None else torch.empty_like(w)
-                gb = (sink_b if sink_b is not None else g.new_empty((Cout,))) if want_gb else None
-                defer = sink_w is not None and _defer_wgrad_ok(ctx.params[2 * i], ctx.params[2 * i + 1] if want_gb else None,
-                                                               flop=18.0 * N * H * W * Cin * Cout)
-                acc = 3 if defer else (1 if sink_w is not None else 0)
-                with _on_side_stream(sink_w is not None, xin, g, mask if fuse else None, flop=18.0 * N * H * W * Cin * Cout):
-                    ws_n = _q("sstem_conv3x3_wgrad_workspace_floats_algo", N, Cin, H, W, Cout, ALGO_MFMA_BF16)
-                    ws = g.new_empty((max(ws_n, 1),))
+                d = _WgradDelivery(ctx.params[2 * i], ctx.params[2 * i + 1], want_gb, w, Cout, g, 18.0 * N * H * W * Cin * Cout)
+                with d.stream(xin, g, mask if fuse else None):
+                    ws, ws_n, _ = _workspace(g, "sstem_conv3x3_wgrad_workspace_floats_algo", N, Cin, H, W, Cout, ALGO_MFMA_BF16)
                     with _on(g.device):
                         if fuse:
                             rc = lib.sstem_conv3x3_backward_weight_bf16_masked(xin.data_ptr(), 1 if xin.dtype == torch.bfloat16 else 0, g.data_ptr(),
-                                                                               mask.data_ptr(), gw.data_ptr(), _ptr(gb), ws.data_ptr(), ws_n,
-                                                                               N, Cin, H, W, Cout, acc, _stream())
+                                                                               mask.data_ptr(), d.gw.data_ptr(), _ptr(d.gb), ws.data_ptr(), ws_n,
+                                                                               N, Cin, H, W, Cout, d.acc, _stream())
                         elif xin.dtype == torch.bfloat16:
-                            rc = lib.sstem_conv3x3_backward_weight_bf16in_ex(xin.data_ptr(), g.data_ptr(), gw.data_ptr(), _ptr(gb), ws.data_ptr(), ws_n,
-                                                                             N, Cin, H, W, Cout, acc, _stream())
+                            rc = lib.sstem_conv3x3_backward_weight_bf16in_ex(xin.data_ptr(), g.data_ptr(), d.gw.data_ptr(), _ptr(d.gb), ws.data_ptr(), ws_n,
+                                                                             N, Cin, H, W, Cout, d.acc, _stream())
                         else:
-                            rc = lib.sstem_conv2d_backward_weight_bias_ex_f32(xin.data_ptr(), g.data_ptr(), gw.data_ptr(), _ptr(gb), ws.data_ptr(), ws_n,
-                                                                              N, Cin, H, W, Cout, 3, 3, 1, 1, acc, _stream(), ALGO_MFMA_BF16)
+                            rc = lib.sstem_conv2d_backward_weight_bias_ex_f32(xin.data_ptr(), g.data_ptr(), d.gw.data_ptr(), _ptr(d.gb), ws.data_ptr(), ws_n,
+                                                                              N, Cin, H, W, Cout, 3, 3, 1, 1, d.acc, _stream(), ALGO_MFMA_BF16)
                     sstem_native.check(rc, "conv chain weight gradient")
-                if sink_w is None:
-                    grads[2 * i], grads[2 * i + 1] = gw, gb
-                elif defer:
-                    _deferred_wgrad_issued(ws, ctx.params[2 * i], ctx.params[2 * i + 1] if want_gb else None)
-                else:
-                    _sink_done(ctx.params[2 * i], ctx.params[2 * i + 1] if want_gb else None)
+                grads[2 * i], grads[2 * i + 1] = d.done(ws)
             elif ctx.has_bias[i] and ctx.needs_input_grad[3 + 2 * i]:
                 grads[2 * i + 1] = g.sum((0, 2, 3))
             if i > 0 or ctx.needs_input_grad[0]:
@@ -1593,17 +1592,17 @@ def conv2d_fused(x, w, b=None, scale=None, shift=None, act=ACT_NONE, slope=0.0, 
         assert pool_out is not None and out is None and not _recording(x, w, b)
         # the checks _Conv2dFused.forward makes (this branch bypasses it): device, dtype, and a contiguous view of everything the launch
         # reads through data_ptr()
-        x = _check(x, "input"); w = _check(w, "weight")
-        b = _check(b, "bias") if b is not None else None
-        scale = _check(scale, "scale") if scale is not None else None
-        shift = _check(shift, "shift") if shift is not None else None
+        x, w, b, scale, shift = _check_forward_args(x, w, b, scale, shift)
         return _raw_conv(x, w, b, scale, shift, act, slope, owner=owner, pool_out=pool_out, pool_kind=pool_kind, pool_only=True)
     res = _Conv2dFused.apply(x, w, b, scale, shift, act, slope, _recording(x, w, b), owner, residual, res_scale, bn_part, out, out_blocked,
                              pool_out, pool_kind)
-    if out is not None and res is not out:       # autograd hands back an alias of a tensor that came in as an argument: the bound rides on
-        word = amax_word_of(out)                 # the object the launch tagged
-        if word is not None:
-            tag_amax(res, word)
+    return _alias_of_out(res, out)
+
+
+def _alias_of_out(res, out):
+    """autograd hands back an ALIAS of a tensor that came in as an argument (out=): the bound rides on the object the launch tagged."""
+    if out is not None and res is not out:
+        hand_on_amax(out, res)
     return res
 
 
@@ -1615,11 +1614,7 @@ def can_store_into(x, w, b=None):
 def conv_transpose3x3s2_fused(x, w, b=None, scale=None, shift=None, act=ACT_NONE, slope=0.0, owner=None, residual=None, res_scale=1.0,
                               bn_part=None, out=None):
     res = _ConvT3x3s2Fused.apply(x, w, b, scale, shift, act, slope, _recording(x, w, b), owner, residual, res_scale, bn_part, out)
-    if out is not None and res is not out:
-        word = amax_word_of(out)
-        if word is not None:
-            tag_amax(res, word)
-    return res
+    return _alias_of_out(res, out)
 
 
 _RESIDUAL_FUSION = os.environ.get("SSTEM_RESIDUAL_FUSION", "1") != "0"      # developer knob (A/B runs)
