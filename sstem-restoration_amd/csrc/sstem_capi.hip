@@ -13,6 +13,7 @@
 #include "../../include/sstem_norm.h"
 #include "../../include/sstem_loss.h"
 #include "../../include/sstem_score.h"
+#include "../../include/sstem_fold.h"
 #include "sepconv_kernels.h"
 #include "conv_kernels.h"
 #include "warp_kernels.h"
@@ -20,6 +21,7 @@
 #include "norm_kernels.h"
 #include "ssim_kernels.h"
 #include "score_kernels.h"
+#include "fold_kernels.h"
 #include <math.h>
 
 namespace {
@@ -233,6 +235,9 @@ int score_images(const char* what, const T* a, const T* b, int64_t B, int64_t H,
     const hipError_t e = sstem::launch_score_images<T>(a, b, B, H, W, plan, clamp01_a ? 1 : 0, scores, workspace, static_cast<hipStream_t>(stream));
     return launched(what, e, " launch");
 }
+
+// ---- fold synthesis (include/sstem_fold.h): the range the kernels index in 32 bits (a plane below 2^30 pixels) ------------------------
+bool fold_range_ok(int64_t n, int64_t H, int64_t W) { return n <= (1 << 24) && H <= 32768 && W <= 32768; }
 
 }  // namespace
 
@@ -1471,6 +1476,53 @@ int sstem_flow_epe_f32(const float* flow, const float* target, int64_t B, int64_
     const hipError_t e = sstem::launch_flow_epe(flow, target, B, H, W, plan, sparse ? 1 : 0, mean ? 1 : 0, value, workspace,
                                                 static_cast<hipStream_t>(stream));
     return launched("flow epe", e, " launch");
+}
+
+// ---- fold synthesis (include/sstem_fold.h) ---------------------------------------------------------------------------------------
+int sstem_fold_flow(const double* folds, int64_t n, int64_t H, int64_t W, float* flow, float* flow2, uint8_t* mask, void* stream)
+{
+    const char* what = "fold flow";
+    if (n < 0 || H < 0 || W < 0) return fail(SSTEM_ERR_BAD_SHAPE, "%s: negative size", what);
+    if (n == 0 || H == 0 || W == 0) return SSTEM_OK;
+    if (!folds) return fail(SSTEM_ERR_NULL_POINTER, "%s: null fold table", what);
+    if (!fold_range_ok(n, H, W)) return fail(SSTEM_ERR_UNSUPPORTED, "%s: sizes past the index range (H, W <= 32768, n <= 2^24)", what);
+    if (!flow && !flow2 && !mask) return SSTEM_OK;
+    return launched(what, sstem::launch_fold_flow(folds, (int)n, (int)H, (int)W, flow, flow2, mask, static_cast<hipStream_t>(stream)), " launch");
+}
+
+int sstem_image_warp_u8(const uint8_t* im, const float* flow, uint8_t* out, int64_t n, int64_t H, int64_t W, int64_t C, int mode,
+                        void* stream)
+{
+    const char* what = "image warp (u8)";
+    if (n < 0 || H < 0 || W < 0) return fail(SSTEM_ERR_BAD_SHAPE, "%s: negative size", what);
+    if (C < 1) return fail(SSTEM_ERR_BAD_SHAPE, "%s: C must be at least 1", what);
+    if (mode != SSTEM_WARP_NEAREST && mode != SSTEM_WARP_BILINEAR) return fail(SSTEM_ERR_UNSUPPORTED, "%s: unknown mode", what);
+    if (n == 0 || H == 0 || W == 0) return SSTEM_OK;
+    if (!im || !flow || !out) return fail(SSTEM_ERR_NULL_POINTER, "%s: null tensor pointer", what);
+    if (!fold_range_ok(n, H, W) || C > 1024)
+        return fail(SSTEM_ERR_UNSUPPORTED, "%s: sizes past the index range (H, W <= 32768, n <= 2^24, C <= 1024)", what);
+    return launched(what, sstem::launch_image_warp_u8(im, flow, out, (int)n, (int)H, (int)W, (int)C, mode == SSTEM_WARP_BILINEAR ? 1 : 0,
+                                                      static_cast<hipStream_t>(stream)), " launch");
+}
+
+int sstem_fold_degrade_u8(const uint8_t* clean, const uint8_t* interp, const double* folds, const int32_t* slot, int64_t n, int64_t slots,
+                          int64_t S_h, int64_t S_w, int64_t off_y, int64_t off_x, int64_t out_h, int64_t out_w, int gt_line,
+                          uint8_t* deformed, float* flow2, float* im, float* lb, int32_t* zero_count, void* stream)
+{
+    const char* what = "fold degrade";
+    if (n < 0 || slots < 0 || S_h < 0 || S_w < 0 || off_y < 0 || off_x < 0 || out_h < 0 || out_w < 0)
+        return fail(SSTEM_ERR_BAD_SHAPE, "%s: negative size", what);
+    if (off_y > S_h || out_h > S_h - off_y || off_x > S_w || out_w > S_w - off_x)
+        return fail(SSTEM_ERR_BAD_SHAPE, "%s: the window is not inside the plane", what);
+    if (n == 0) return SSTEM_OK;
+    if (!clean || !folds) return fail(SSTEM_ERR_NULL_POINTER, "%s: null plane or fold table", what);
+    if (im && !interp) return fail(SSTEM_ERR_NULL_POINTER, "%s: im needs the interp plane", what);
+    if (!fold_range_ok(n, S_h, S_w) || slots > (1 << 24))
+        return fail(SSTEM_ERR_UNSUPPORTED, "%s: sizes past the index range (S_h, S_w <= 32768, n, slots <= 2^24)", what);
+    if (!deformed && !flow2 && !im && !lb && !zero_count) return SSTEM_OK;
+    return launched(what, sstem::launch_fold_degrade(clean, interp, folds, slot, (int)n, (int)slots, (int)S_h, (int)S_w, (int)off_y, (int)off_x,
+                                                     (int)out_h, (int)out_w, gt_line ? 1 : 0, deformed, flow2, im, lb, zero_count,
+                                                     static_cast<hipStream_t>(stream)), " launch");
 }
 
 }  // extern "C"
