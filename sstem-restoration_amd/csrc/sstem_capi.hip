@@ -14,6 +14,7 @@
 #include "../../include/sstem_loss.h"
 #include "../../include/sstem_score.h"
 #include "../../include/sstem_fold.h"
+#include "../../include/sstem_batch.h"
 #include "sepconv_kernels.h"
 #include "conv_kernels.h"
 #include "warp_kernels.h"
@@ -22,6 +23,7 @@
 #include "ssim_kernels.h"
 #include "score_kernels.h"
 #include "fold_kernels.h"
+#include "batch_kernels.h"
 #include <math.h>
 
 namespace {
@@ -1523,6 +1525,61 @@ int sstem_fold_degrade_u8(const uint8_t* clean, const uint8_t* interp, const dou
     return launched(what, sstem::launch_fold_degrade(clean, interp, folds, slot, (int)n, (int)slots, (int)S_h, (int)S_w, (int)off_y, (int)off_x,
                                                      (int)out_h, (int)out_w, gt_line ? 1 : 0, deformed, flow2, im, lb, zero_count,
                                                      static_cast<hipStream_t>(stream)), " launch");
+}
+
+}  // extern "C"
+
+// ---- training crops (include/sstem_batch.h) ----------------------------------------------------------------------------------------
+namespace {
+
+// the checks the two crop entries share; `done` is set when the call is a successful no-op
+int crop_orient_checks(const char* what, const void* pool, const void* images, int64_t n_images, const void* samples, const void* plane_image,
+                       int64_t n, int64_t P, int64_t S_h, int64_t S_w, int64_t C0, int64_t C1, bool* done)
+{
+    *done = false;
+    if (n_images < 0 || n < 0 || S_h < 0 || S_w < 0 || C0 < 0 || C1 < 0) return fail(SSTEM_ERR_BAD_SHAPE, "%s: negative size", what);
+    if (P < 1) return fail(SSTEM_ERR_BAD_SHAPE, "%s: P must be at least 1", what);
+    if (P > SSTEM_BATCH_MAX_PLANES || C0 + C1 > SSTEM_BATCH_MAX_CHANNELS)
+        return fail(SSTEM_ERR_UNSUPPORTED, "%s: more than 16 planes or channels", what);
+    if (S_h > 32768 || S_w > 32768 || n > (1 << 24) || n_images > (1 << 24))
+        return fail(SSTEM_ERR_UNSUPPORTED, "%s: sizes past the index range (S_h, S_w <= 32768, n, n_images <= 2^24)", what);
+    if (n == 0 || S_h == 0 || S_w == 0) { *done = true; return SSTEM_OK; }
+    if (!pool || !images || !samples || !plane_image) return fail(SSTEM_ERR_NULL_POINTER, "%s: null pool or table", what);
+    return SSTEM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sstem_crop_orient_u8(const uint8_t* pool, const int64_t* images, int64_t n_images, const int32_t* samples, const int32_t* plane_image,
+                         int64_t n, int64_t P, int64_t S_h, int64_t S_w, uint8_t* out, void* stream)
+{
+    const char* what = "crop orient (u8)";
+    bool done;
+    const int rc = crop_orient_checks(what, pool, images, n_images, samples, plane_image, n, P, S_h, S_w, 0, 0, &done);
+    if (rc != SSTEM_OK || done) return rc;
+    if (!out) return fail(SSTEM_ERR_NULL_POINTER, "%s: null output", what);
+    return launched(what, sstem::launch_crop_orient_u8(pool, images, (int)n_images, samples, plane_image, (int)n, (int)P, (int)S_h, (int)S_w, out,
+                                                       static_cast<hipStream_t>(stream)), " launch");
+}
+
+int sstem_crop_orient_f32(const uint8_t* pool, const int64_t* images, int64_t n_images, const int32_t* samples, const int32_t* plane_image,
+                          int64_t n, int64_t P, int64_t S_h, int64_t S_w, const int32_t* chan_plane, int64_t C0, int64_t C1,
+                          uint32_t chan_invert, float* out0, float* out1, void* stream)
+{
+    const char* what = "crop orient (f32)";
+    bool done;
+    const int rc = crop_orient_checks(what, pool, images, n_images, samples, plane_image, n, P, S_h, S_w, C0, C1, &done);
+    if (rc != SSTEM_OK) return rc;
+    if (C0 < 1) return fail(SSTEM_ERR_BAD_SHAPE, "%s: C0 must be at least 1", what);
+    if (done) return SSTEM_OK;
+    if (!chan_plane || !out0 || (C1 > 0 && !out1)) return fail(SSTEM_ERR_NULL_POINTER, "%s: null channel map or output", what);
+    for (int64_t c = 0; c < C0 + C1; ++c)
+        if (chan_plane[c] < 0 || chan_plane[c] >= P) return fail(SSTEM_ERR_BAD_SHAPE, "%s: a channel's plane is outside [0, P)", what);
+    return launched(what, sstem::launch_crop_orient_f32(pool, images, (int)n_images, samples, plane_image, (int)n, (int)P, (int)S_h, (int)S_w,
+                                                        chan_plane, (int)C0, (int)C1, chan_invert, out0, out1,
+                                                        static_cast<hipStream_t>(stream)), " launch");
 }
 
 }  // extern "C"

@@ -4,10 +4,13 @@ its ``__getitem__`` (``sff_scripts_fusion/data/data_provider.py:142-169,183-248`
 The host keeps what is random or file-bound (reading, crop positions, flips, jitter -- and drawing the fold, ``draw_fold``); the device
 does the arithmetic: per attempt ONE call of ``sstem_fold_degrade_u8`` (``include/sstem_fold.h``) warps every sample's uint8 crop by its
 fold, masks the fold line, crops the centre window, counts the black pixels and writes the fp32 batch -- bit for bit the reference's
-numbers.  A batch leaves the host as two uint8 crops per sample instead of 6 + 1 fp32 planes.
+numbers.  A batch leaves the host as two uint8 crops per sample instead of 6 + 1 fp32 planes -- or, with the sections resident on the
+device (``data/resident.py``), as a few integers per sample: ``batch_resident`` draws the crops, cuts and orients them in one launch
+of ``sstem_crop_orient_u8`` and runs the same rounds on its output.
 
     synth = FoldSynthesizer(det_size=256)
     batch = synth.batch(clean_u8, interp_u8, random)          # [B,400,400] uint8 GPU tensors -> im [B,6,256,256], lb [B,1,256,256]
+    batch = synth.batch_resident(resident, pairs, random, 16, 400, flags)      # the same from a ResidentImages set
     step.load(batch.im, batch.lb)
 
 GPU tensors only -- there is no CPU fallback.
@@ -15,6 +18,8 @@ GPU tensors only -- there is no CPU fallback.
 import torch
 
 import sstem_native
+from data.interp_batch import draw_orientation
+from data.resident import crop_u8, sample_table
 from utils.flow_synthesis import FOLD_PARAMS, fold_scalars, gen_line
 
 
@@ -42,6 +47,19 @@ def draw_fold(rng, height, width):
     dis_k = rng.uniform(0.00001, 0.1)
     k, b = gen_line(points[0], points[1])
     return k, b, line_width, fold_width, dis_k
+
+
+def draw_fusion_crop(rng, flags, shapes, crop):
+    """One crop ``(k, i, j, code)`` from ``rng``, consuming it exactly as the fusion and unfolding providers' ``__getitem__`` does
+    (``data_provider.py:111-137``): the pair, the window's row and column, the flips, the rotation.  The provider's ``swap`` indexes a
+    third plane that its two-plane stack does not have, so ``flags.swap`` is refused."""
+    if flags.swap:
+        raise ValueError("the fusion provider's swap indexes a third plane it does not have")
+    k = rng.randint(0, len(shapes) - 1)
+    H, W = shapes[k]
+    i = rng.randint(0, H - crop[0])
+    j = rng.randint(0, W - crop[1])
+    return k, i, j, draw_orientation(rng, flags)
 
 
 class FoldBatch(object):
@@ -139,4 +157,21 @@ class FoldSynthesizer(object):
         if out is None:
             out = FoldBatch(0, window, label, clean_u8.device)
         out.folds, out.drawn, out.rounds = folds, drawn, rounds
+        return out
+
+    def batch_resident(self, resident, pairs, rng, B, crop_size, flags, label="image", gt_line=False):
+        """The batch from a device-resident set (``data/resident.py``): ``pairs[k]`` names the resident images (section, its
+        interpolation) of training entry k.  Draws the B crops in slot order, cuts and orients them in one launch (``crop_u8``: its planes
+        0 and 1 are ``clean`` and ``interp``), then runs ``batch`` on them -- no crop leaves the host.  With B == 1 the stream is
+        consumed as the reference's ``__getitem__`` consumes it; with more, all crop draws come first, then the fold rounds."""
+        pairs = [tuple(p) for p in pairs]
+        shapes = [resident.shapes[p[0]] for p in pairs]
+        samples, planes = [], []
+        for _ in range(B):
+            k, i, j, code = draw_fusion_crop(rng, flags, shapes, (crop_size, crop_size))
+            samples.append((i, j, code))
+            planes.append(pairs[k])
+        crops = crop_u8(resident, sample_table(samples, planes, resident.device), crop_size, crop_size)
+        out = self.batch(crops[0], crops[1], rng, label, gt_line)
+        out.crops = samples
         return out
