@@ -7,7 +7,8 @@
  *   gen_flow(height, width, k, b, line_width, fold_width, dis_k)    utils/flow_synthesis.py:20-87
  *   image_warp(im, flow, mode)                                      utils/image_warp.py:3-112
  *   (deformed * mask).astype(np.uint8), the centre crop, the count of black pixels, np.repeat(.., 3, 0), astype(np.float32) / 255.0
- * Drawing the fold (the random module), reading files and colour jitter stay on the host.  The crops and flips ahead of the fold can
+ * Drawing the fold (the random module) and reading files stay on the host; colour jitter is built in sstem_jitter.h (a byte table per
+ * sample, read through by sstem_fold_degrade_lut_u8; only drawing its factors stays on the host).  The crops and flips ahead of the fold can
  * stay there too, or come from sstem_crop_orient_u8 (sstem_batch.h), whose planes 0 and 1 are this header's clean and interp.
  *
  * A fold is a row of SSTEM_FOLD_PARAMS doubles, derived on the host with the reference's own Python expressions (so the library

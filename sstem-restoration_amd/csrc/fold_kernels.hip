@@ -3,7 +3,7 @@
 // Replaces the host arithmetic of the reference's Train.degradation (sff_scripts_fusion/data/data_provider.py:183-248): ~30 float64
 // numpy passes over a 400 x 400 plane per candidate fold (utils/flow_synthesis.py:20-87), a bilinear back-warp of the uint8 crop
 // (utils/image_warp.py:3-112), the mask product, the centre crop and the /255 replication to six fp32 channels.  A pure per-pixel map
-// with a 4-point byte gather: streaming kernels, no MFMA, no LDS.  256 threads, one pixel per thread, x innermost (every store is
+// with a 4-point byte gather: streaming kernels, no MFMA, no LDS (but the 256-byte jitter table of fold_degrade<true>).  256 threads, one pixel per thread, x innermost (every store is
 // coalesced), the sample from blockIdx.y so a block's fold row is wave-uniform (scalar loads), a grid-stride walk under a capped grid.
 //
 // The contract is bit for bit with the reference, so every expression below restates numpy's operation order literally: separate
@@ -140,25 +140,35 @@ __global__ __launch_bounds__(256) void fold_clear_counts(const int32_t* __restri
     }
 }
 
+// The fused sample.  LUT (include/sstem_jitter.h): the four bytes gathered for the warp go through the slot's 256-entry table, staged in
+// LDS once per sample; the label still reads the plane itself.  Without LUT it is the kernel it always was (lut is not read).
+template <bool LUT>
 __global__ __launch_bounds__(256) void fold_degrade(const uint8_t* __restrict__ clean, const uint8_t* __restrict__ interp,
                                                     const double* __restrict__ folds, const int32_t* __restrict__ slot, int n, int slots,
                                                     int SH, int SW, int off_y, int off_x, int out_h, int out_w, int gt_line,
                                                     uint8_t* __restrict__ deformed, float* __restrict__ flow2, float* __restrict__ im,
-                                                    float* __restrict__ lb, int32_t* __restrict__ zero_count)
+                                                    float* __restrict__ lb, int32_t* __restrict__ zero_count, const uint8_t* __restrict__ lut)
 {
+    __shared__ uint8_t table[LUT ? 256 : 1];
     const int64_t plane = (int64_t)SH * SW, win = (int64_t)out_h * out_w;
     for (int s = blockIdx.y; s < n; s += gridDim.y) {
         const int sl = slot ? slot[s] : s;                                   // block-uniform
         if (sl < 0 || sl >= slots) continue;
         const double* f = folds + (int64_t)s * SSTEM_FOLD_PARAMS;
         const uint8_t* src = clean + (int64_t)sl * plane;
+        if (LUT) {
+            __syncthreads();                                                 // the previous sample's reads of the table are done
+            table[threadIdx.x] = lut[(int64_t)sl * 256 + threadIdx.x];
+            __syncthreads();
+        }
         int zeros = 0;
         for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < win; p += (int64_t)gridDim.x * 256) {
             const int wy = (int)((uint32_t)p / (uint32_t)out_w), wx = (int)((uint32_t)p - (uint32_t)wy * (uint32_t)out_w);
             const int y = off_y + wy, x = off_x + wx;
             const FoldPixel px = fold_pixel(f, x, y);
             const WarpTaps t = warp_taps(px.fx, px.fy, x, y, SH, SW);
-            const uint8_t w = warp_blend(t, (float)src[t.a], (float)src[t.b], (float)src[t.c], (float)src[t.d]);
+            const uint8_t w = LUT ? warp_blend(t, (float)table[src[t.a]], (float)table[src[t.b]], (float)table[src[t.c]], (float)table[src[t.d]])
+                                  : warp_blend(t, (float)src[t.a], (float)src[t.b], (float)src[t.c], (float)src[t.d]);
             const uint8_t d = px.mask ? w : (uint8_t)0;                      // data_provider.py:233 (deformed * mask).astype(np.uint8)
             zeros += d == 0 ? 1 : 0;                                         // :239-240
             const int64_t o = (int64_t)sl * win + p;
@@ -212,7 +222,7 @@ hipError_t launch_image_warp_u8(const uint8_t* im, const float* flow, uint8_t* o
 
 hipError_t launch_fold_degrade(const uint8_t* clean, const uint8_t* interp, const double* folds, const int32_t* slot, int n, int slots, int SH,
                                int SW, int off_y, int off_x, int out_h, int out_w, int gt_line, uint8_t* deformed, float* flow2, float* im,
-                               float* lb, int32_t* zero_count, hipStream_t s)
+                               float* lb, int32_t* zero_count, hipStream_t s, const uint8_t* lut)
 {
     if (zero_count) {
         int g = (n + 255) / 256;
@@ -222,8 +232,13 @@ hipError_t launch_fold_degrade(const uint8_t* clean, const uint8_t* interp, cons
         if (e != hipSuccess) return e;
     }
     if (out_h == 0 || out_w == 0) return hipSuccess;
-    hipLaunchKernelGGL(fold_degrade, fold_grid(n, (int64_t)out_h * out_w), dim3(256), 0, s, clean, interp, folds, slot, n, slots, SH, SW, off_y,
-                       off_x, out_h, out_w, gt_line, deformed, flow2, im, lb, zero_count);
+    const dim3 grid = fold_grid(n, (int64_t)out_h * out_w);
+    if (lut)
+        hipLaunchKernelGGL(fold_degrade<true>, grid, dim3(256), 0, s, clean, interp, folds, slot, n, slots, SH, SW, off_y, off_x, out_h, out_w,
+                           gt_line, deformed, flow2, im, lb, zero_count, lut);
+    else
+        hipLaunchKernelGGL(fold_degrade<false>, grid, dim3(256), 0, s, clean, interp, folds, slot, n, slots, SH, SW, off_y, off_x, out_h, out_w,
+                           gt_line, deformed, flow2, im, lb, zero_count, lut);
     return hipGetLastError();
 }
 

@@ -14,6 +14,7 @@
 #include "../../include/sstem_loss.h"
 #include "../../include/sstem_score.h"
 #include "../../include/sstem_fold.h"
+#include "../../include/sstem_jitter.h"
 #include "../../include/sstem_batch.h"
 #include "sepconv_kernels.h"
 #include "conv_kernels.h"
@@ -23,6 +24,7 @@
 #include "ssim_kernels.h"
 #include "score_kernels.h"
 #include "fold_kernels.h"
+#include "jitter_kernels.h"
 #include "batch_kernels.h"
 #include <math.h>
 
@@ -1480,6 +1482,34 @@ int sstem_flow_epe_f32(const float* flow, const float* target, int64_t B, int64_
     return launched("flow epe", e, " launch");
 }
 
+}  // extern "C"
+
+namespace {
+
+// sstem_fold_degrade_u8 and, with a table, sstem_fold_degrade_lut_u8 (include/sstem_jitter.h): one set of checks, one launcher
+int fold_degrade_entry(const char* what, const uint8_t* clean, const uint8_t* interp, const double* folds, const int32_t* slot, int64_t n,
+                       int64_t slots, int64_t S_h, int64_t S_w, int64_t off_y, int64_t off_x, int64_t out_h, int64_t out_w, int gt_line,
+                       const uint8_t* lut, uint8_t* deformed, float* flow2, float* im, float* lb, int32_t* zero_count, void* stream)
+{
+    if (n < 0 || slots < 0 || S_h < 0 || S_w < 0 || off_y < 0 || off_x < 0 || out_h < 0 || out_w < 0)
+        return fail(SSTEM_ERR_BAD_SHAPE, "%s: negative size", what);
+    if (off_y > S_h || out_h > S_h - off_y || off_x > S_w || out_w > S_w - off_x)
+        return fail(SSTEM_ERR_BAD_SHAPE, "%s: the window is not inside the plane", what);
+    if (n == 0) return SSTEM_OK;
+    if (!clean || !folds) return fail(SSTEM_ERR_NULL_POINTER, "%s: null plane or fold table", what);
+    if (im && !interp) return fail(SSTEM_ERR_NULL_POINTER, "%s: im needs the interp plane", what);
+    if (!fold_range_ok(n, S_h, S_w) || slots > (1 << 24))
+        return fail(SSTEM_ERR_UNSUPPORTED, "%s: sizes past the index range (S_h, S_w <= 32768, n, slots <= 2^24)", what);
+    if (!deformed && !flow2 && !im && !lb && !zero_count) return SSTEM_OK;
+    return launched(what, sstem::launch_fold_degrade(clean, interp, folds, slot, (int)n, (int)slots, (int)S_h, (int)S_w, (int)off_y, (int)off_x,
+                                                     (int)out_h, (int)out_w, gt_line ? 1 : 0, deformed, flow2, im, lb, zero_count,
+                                                     static_cast<hipStream_t>(stream), lut), " launch");
+}
+
+}  // namespace
+
+extern "C" {
+
 // ---- fold synthesis (include/sstem_fold.h) ---------------------------------------------------------------------------------------
 int sstem_fold_flow(const double* folds, int64_t n, int64_t H, int64_t W, float* flow, float* flow2, uint8_t* mask, void* stream)
 {
@@ -1511,20 +1541,30 @@ int sstem_fold_degrade_u8(const uint8_t* clean, const uint8_t* interp, const dou
                           int64_t S_h, int64_t S_w, int64_t off_y, int64_t off_x, int64_t out_h, int64_t out_w, int gt_line,
                           uint8_t* deformed, float* flow2, float* im, float* lb, int32_t* zero_count, void* stream)
 {
-    const char* what = "fold degrade";
-    if (n < 0 || slots < 0 || S_h < 0 || S_w < 0 || off_y < 0 || off_x < 0 || out_h < 0 || out_w < 0)
-        return fail(SSTEM_ERR_BAD_SHAPE, "%s: negative size", what);
-    if (off_y > S_h || out_h > S_h - off_y || off_x > S_w || out_w > S_w - off_x)
-        return fail(SSTEM_ERR_BAD_SHAPE, "%s: the window is not inside the plane", what);
-    if (n == 0) return SSTEM_OK;
-    if (!clean || !folds) return fail(SSTEM_ERR_NULL_POINTER, "%s: null plane or fold table", what);
-    if (im && !interp) return fail(SSTEM_ERR_NULL_POINTER, "%s: im needs the interp plane", what);
-    if (!fold_range_ok(n, S_h, S_w) || slots > (1 << 24))
-        return fail(SSTEM_ERR_UNSUPPORTED, "%s: sizes past the index range (S_h, S_w <= 32768, n, slots <= 2^24)", what);
-    if (!deformed && !flow2 && !im && !lb && !zero_count) return SSTEM_OK;
-    return launched(what, sstem::launch_fold_degrade(clean, interp, folds, slot, (int)n, (int)slots, (int)S_h, (int)S_w, (int)off_y, (int)off_x,
-                                                     (int)out_h, (int)out_w, gt_line ? 1 : 0, deformed, flow2, im, lb, zero_count,
-                                                     static_cast<hipStream_t>(stream)), " launch");
+    return fold_degrade_entry("fold degrade", clean, interp, folds, slot, n, slots, S_h, S_w, off_y, off_x, out_h, out_w, gt_line, nullptr,
+                              deformed, flow2, im, lb, zero_count, stream);
+}
+
+// ---- colour jitter (include/sstem_jitter.h) -------------------------------------------------------------------------------------------
+int sstem_jitter_lut_u8(const uint8_t* planes, int64_t n, int64_t S_h, int64_t S_w, const int32_t* op_code, const float* op_factor,
+                        uint8_t* lut, uint32_t* hist, void* stream)
+{
+    const char* what = "jitter lut";
+    if (n < 0 || S_h < 0 || S_w < 0) return fail(SSTEM_ERR_BAD_SHAPE, "%s: negative size", what);
+    if (!fold_range_ok(n, S_h, S_w)) return fail(SSTEM_ERR_UNSUPPORTED, "%s: sizes past the index range (S_h, S_w <= 32768, n <= 2^24)", what);
+    if (n == 0 || S_h == 0 || S_w == 0) return SSTEM_OK;
+    if (!planes || !op_code || !op_factor || !lut || !hist) return fail(SSTEM_ERR_NULL_POINTER, "%s: null plane, step table, lut or hist", what);
+    return launched(what, sstem::launch_jitter_lut(planes, (int)n, S_h * S_w, op_code, op_factor, lut, hist, static_cast<hipStream_t>(stream)),
+                    " launch");
+}
+
+int sstem_fold_degrade_lut_u8(const uint8_t* clean, const uint8_t* interp, const double* folds, const int32_t* slot, int64_t n,
+                              int64_t slots, int64_t S_h, int64_t S_w, int64_t off_y, int64_t off_x, int64_t out_h, int64_t out_w,
+                              int gt_line, const uint8_t* lut, uint8_t* deformed, float* flow2, float* im, float* lb,
+                              int32_t* zero_count, void* stream)
+{
+    return fold_degrade_entry("fold degrade (lut)", clean, interp, folds, slot, n, slots, S_h, S_w, off_y, off_x, out_h, out_w, gt_line, lut,
+                              deformed, flow2, im, lb, zero_count, stream);
 }
 
 }  // extern "C"
