@@ -13,7 +13,8 @@
  *   running_mean / _var    [C] or NULL (not tracked); updated in place by the forward
  *   save_mean, save_invstd [C], written by the forward, read by the backward
  *   act                    0 none, 1 ReLU, 2 LeakyReLU(slope) -- applied after the affine; the backward recomputes the
- *                          activation mask from x, so nothing else is kept from the forward
+ *                          pre-activation from x exactly as the forward formed it (same weight, bias, save_mean and
+ *                          save_invstd), so its mask is that of the stored y and nothing else is kept from the forward
  *   dweight, dbias         [C] or NULL
  *   workspace              sstem_batchnorm_workspace_floats(N, C, HW) floats, device, caller-allocated
  * Fixed summation order (bitwise reproducible).  Same status codes / error reporting / stream and ownership rules as

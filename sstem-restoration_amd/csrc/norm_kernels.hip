@@ -52,6 +52,21 @@ __device__ __forceinline__ float act_grad(float pre, int act, float slope)      
     return act == 1 ? (pre > 0.f ? 1.f : 0.f) : (act == 2 ? (pre > 0.f ? 1.f : slope) : 1.f);
 }
 
+// The affine of a channel folded into one multiply-add, and the pre-activation value it gives.  The forward stores act(pre) and the
+// backward takes act'(pre) from the SAME floats (save_mean, save_invstd, weight, bias) through these two functions, with the
+// multiply-adds spelled out, so the two agree in sign at every element by construction and not by how the compiler happens to contract
+// two call sites: a pre-activation recomputed as ((x - mean) * invstd) * w + b rounds differently and, on flat regions whose repeated
+// value lands within an ulp of the threshold, took the other side at every such element.
+struct BnAffine { float sc, sf; };
+__device__ __forceinline__ BnAffine bn_affine(float mean, float invstd, const float* __restrict__ weight, const float* __restrict__ bias, int c)
+{
+    BnAffine a;
+    a.sc = invstd * (weight ? weight[c] : 1.f);
+    a.sf = fmaf(-mean, a.sc, bias ? bias[c] : 0.f);
+    return a;
+}
+__device__ __forceinline__ float bn_pre(float x, const BnAffine& a) { return fmaf(x, a.sc, a.sf); }
+
 // COH (the one-launch forms, round 5): partials written by workgroups on other XCDs are read inside the same launch -- the eight L2s are
 // not coherent with one another within a launch, so those few floats go past them (agent-scope stores and loads)
 template <bool COH> __device__ __forceinline__ float ld_part(const float* p)
@@ -201,8 +216,7 @@ __device__ __forceinline__ void bn_fwd_apply_body(const float* __restrict__ x, c
             running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
         }
     }
-    const float sc = invstd * (weight ? weight[c] : 1.f);
-    const float sf = (bias ? bias[c] : 0.f) - mean * sc;
+    const BnAffine af = bn_affine(mean, invstd, weight, bias, c);
     int64_t base, len;
     chunk_span(gm, chunk, c, base, len);
     const float* p = x + base;
@@ -213,14 +227,14 @@ __device__ __forceinline__ void bn_fwd_apply_body(const float* __restrict__ x, c
         float4* o4 = reinterpret_cast<float4*>(o);
         for (int64_t i = threadIdx.x; i < len / 4; i += BN_THREADS) {
             const float4 v = p4[i];
-            const float4 r = make_float4(act_fwd(v.x * sc + sf, act, slope), act_fwd(v.y * sc + sf, act, slope),
-                                         act_fwd(v.z * sc + sf, act, slope), act_fwd(v.w * sc + sf, act, slope));
+            const float4 r = make_float4(act_fwd(bn_pre(v.x, af), act, slope), act_fwd(bn_pre(v.y, af), act, slope),
+                                         act_fwd(bn_pre(v.z, af), act, slope), act_fwd(bn_pre(v.w, af), act, slope));
             o4[i] = r;
             vmax = fmaxf(fmaxf(vmax, fmaxf(fabsf(r.x), fabsf(r.y))), fmaxf(fabsf(r.z), fabsf(r.w)));
         }
-        for (int64_t i = (len / 4) * 4 + threadIdx.x; i < len; i += BN_THREADS) { const float r = act_fwd(p[i] * sc + sf, act, slope); o[i] = r; vmax = fmaxf(vmax, fabsf(r)); }
+        for (int64_t i = (len / 4) * 4 + threadIdx.x; i < len; i += BN_THREADS) { const float r = act_fwd(bn_pre(p[i], af), act, slope); o[i] = r; vmax = fmaxf(vmax, fabsf(r)); }
     } else {
-        for (int64_t i = threadIdx.x; i < len; i += BN_THREADS) { const float r = act_fwd(p[i] * sc + sf, act, slope); o[i] = r; vmax = fmaxf(vmax, fabsf(r)); }
+        for (int64_t i = threadIdx.x; i < len; i += BN_THREADS) { const float r = act_fwd(bn_pre(p[i], af), act, slope); o[i] = r; vmax = fmaxf(vmax, fabsf(r)); }
     }
     if (y_amax) bn_amax_update(y_amax, vmax, sh);
 }
@@ -282,8 +296,9 @@ __global__ __launch_bounds__(BN_THREADS) void bn_fwd_coop(const float* __restric
 }
 
 // ---- backward pass 1: per-chunk sums of dz and dz * xhat, dz = dy * act'(pre-activation) ----------------------
-// The activation mask is recomputed from x (pre = xhat * w + b): nothing but x, the two saved statistics and the
-// affine parameters is kept from the forward.
+// The activation mask is recomputed from x: nothing but x, the two saved statistics and the affine parameters is kept from the
+// forward.  It is taken at bn_pre(x, bn_affine(..)), the very value whose activation the forward stored (the same floats through the
+// same two fmaf), so it is the mask of the stored y, as torch's; xhat is formed on its own for the sums and the dx formula.
 template <bool COH>
 __device__ __forceinline__ void bn_bwd_partial_body(const float* __restrict__ dy, const float* __restrict__ x,
                                                     const float* __restrict__ weight, const float* __restrict__ bias,
@@ -292,7 +307,7 @@ __device__ __forceinline__ void bn_bwd_partial_body(const float* __restrict__ dy
 {
     const int c = blockIdx.y, chunk = blockIdx.x;
     const float mean = save_mean[c], invstd = save_invstd[c];
-    const float w = weight ? weight[c] : 1.f, b = bias ? bias[c] : 0.f;
+    const BnAffine af = bn_affine(mean, invstd, weight, bias, c);
     int64_t base, len;
     chunk_span(gm, chunk, c, base, len);
     const float* px = x + base;
@@ -300,7 +315,7 @@ __device__ __forceinline__ void bn_bwd_partial_body(const float* __restrict__ dy
     float s = 0.f, q = 0.f;
     auto one = [&](float xv, float gv) __attribute__((always_inline)) {
         const float xh = (xv - mean) * invstd;
-        const float dz = gv * act_grad(xh * w + b, act, slope);
+        const float dz = gv * act_grad(bn_pre(xv, af), act, slope);
         s += dz; q += dz * xh;
     };
     if ((base & 3) == 0) {        // 16-byte loads (a first version with scalar loads had a 0.095 ms floor on small tensors)
@@ -349,8 +364,8 @@ __device__ __forceinline__ void bn_bwd_apply_body(const float* __restrict__ dy, 
     const double cnt = (double)gm.N * (double)gm.HW;
     const float m_dz = (float)(sdz / cnt), m_dzx = (float)(sdzx / cnt);
     const float mean = save_mean[c], invstd = save_invstd[c];
-    const float w = weight ? weight[c] : 1.f, b = bias ? bias[c] : 0.f;
-    const float k = w * invstd;
+    const BnAffine af = bn_affine(mean, invstd, weight, bias, c);
+    const float k = (weight ? weight[c] : 1.f) * invstd;
     int64_t base, len;
     chunk_span(gm, chunk, c, base, len);
     const float* px = x + base;
@@ -359,7 +374,7 @@ __device__ __forceinline__ void bn_bwd_apply_body(const float* __restrict__ dy, 
     float vmax = 0.f;
     auto one = [&](float xv, float gv) __attribute__((always_inline)) -> float {
         const float xh = (xv - mean) * invstd;
-        const float dz = gv * act_grad(xh * w + b, act, slope);
+        const float dz = gv * act_grad(bn_pre(xv, af), act, slope);
         return k * (dz - m_dz - xh * m_dzx);
     };
     if ((base & 3) == 0) {

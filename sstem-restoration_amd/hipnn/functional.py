@@ -1838,8 +1838,10 @@ def pool_module(m, x):
 
 class _BatchNormTrainAct(torch.autograd.Function):
     """Train-mode BatchNorm2d (+ ReLU / LeakyReLU) as two native streaming passes forward and two backward
-    (include/sstem_norm.h).  Saves x, the affine parameters and the two per-channel statistics only: the activation mask is
-    recomputed from x in the backward.  running_mean / running_var are updated in place by the forward launch."""
+    (include/sstem_norm.h).  Saves x, the affine parameters and the two per-channel statistics only: the backward recomputes the
+    pre-activation from x with the forward's own expression (the same floats through the same two multiply-adds), so its
+    activation mask is the mask of the y stored here, as torch's is.  running_mean / running_var are updated in place by the
+    forward launch."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, act, slope, partials=None, nbt=None):
