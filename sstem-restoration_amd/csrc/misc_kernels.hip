@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "misc_kernels.h"
+#include "numpy_u8.h"
 #include "wg_reduce.h"
 
 namespace sstem {
@@ -531,12 +532,7 @@ __global__ __launch_bounds__(256) void f32_to_gray_u8(const float* __restrict__ 
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
         float p = pred[i];
         if (clamp01) p = p > 1.f ? 1.f : (p < 0.f ? 0.f : p);          // TrainTensor2mask, gray2tensor.py:26-31
-        const float v = mul_rn(p, 255.0f);
-        // numpy's float -> uint8 astype on x86-64: truncate toward zero to a wide integer, keep the low 8 bits
-        // (no clamp: 256.0 -> 0, -1.0 -> 255); NaN and |v| >= 2^63 -> 0
-        long long w = 0;
-        if (v == v && fabsf(v) < 9.0e18f) w = (long long)v;
-        out[i] = (uint8_t)(w & 0xFF);
+        out[i] = numpy_u8_of(p);                                       // numpy_u8.h: fp32 multiply, truncation, low 8 bits, no clamp
     }
 }
 

@@ -34,6 +34,7 @@
 #include <unordered_map>
 
 #include "sepconv_kernels.h"
+#include "numpy_u8.h"     // numpy_u8_of: (pred * 255).astype(np.uint8), the store of the trusted-gray apply
 
 #ifndef SSTEM_HPF
 #define SSTEM_HPF 11     // trusted-gray kernel, B-operand prefetch: next-row horizontal taps requested per MFMA group (11: all by group 4)
@@ -361,16 +362,6 @@ struct FusedArgs {
                             // multiply, truncation toward zero, low 8 bits, NO clamp (sff_scripts_interp/inference_singleImage.py:76) --
                             // [B,H,W] bytes, stored by the launch that holds the value
 };
-
-// (pred * 255).astype(np.uint8) as numpy does it on x86-64 (misc_kernels.hip, f32_to_gray_u8): truncate to a wide integer, low 8 bits;
-// NaN and |v| >= 2^63 give 0
-__device__ __forceinline__ uint8_t numpy_u8_of(float p)
-{
-    const float v = __fmul_rn(p, 255.0f);
-    long long w = 0;
-    if (v == v && fabsf(v) < 9.0e18f) w = (long long)v;
-    return (uint8_t)(w & 0xFF);
-}
 
 // Forward (MODE 0), gradVertical (MODE 1) and the fused interpolation apply (MODE 2) share the T-tile
 // pipeline.

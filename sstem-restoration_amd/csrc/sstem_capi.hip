@@ -16,6 +16,7 @@
 #include "../../include/sstem_fold.h"
 #include "../../include/sstem_jitter.h"
 #include "../../include/sstem_batch.h"
+#include "../../include/sstem_display.h"
 #include "sepconv_kernels.h"
 #include "conv_kernels.h"
 #include "warp_kernels.h"
@@ -26,6 +27,7 @@
 #include "fold_kernels.h"
 #include "jitter_kernels.h"
 #include "batch_kernels.h"
+#include "display_kernels.h"
 #include <math.h>
 
 namespace {
@@ -1620,6 +1622,56 @@ int sstem_crop_orient_f32(const uint8_t* pool, const int64_t* images, int64_t n_
     return launched(what, sstem::launch_crop_orient_f32(pool, images, (int)n_images, samples, plane_image, (int)n, (int)P, (int)S_h, (int)S_w,
                                                         chan_plane, (int)C0, (int)C1, chan_invert, out0, out1,
                                                         static_cast<hipStream_t>(stream)), " launch");
+}
+
+}  // extern "C"
+
+// ---- image outputs (include/sstem_display.h) ------------------------------------------------------------------------------------------
+namespace {
+
+// the checks the two display entries share, ahead of their pointers; `done` is set when the call is a successful no-op
+int display_checks(const char* what, int64_t B, int64_t H, int64_t W, bool* done)
+{
+    *done = false;
+    if (B < 0 || H < 0 || W < 0) return fail(SSTEM_ERR_BAD_SHAPE, "%s: negative size", what);
+    if (!fold_range_ok(B, H, W)) return fail(SSTEM_ERR_UNSUPPORTED, "%s: sizes past the index range (H, W <= 32768, B <= 2^24)", what);
+    if (B == 0 || H == 0 || W == 0) *done = true;
+    return SSTEM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const uint8_t* sstem_flow_color_wheel(void) { return sstem::flow_color_wheel(); }
+
+int64_t sstem_flow_color_workspace_bytes(int64_t B) { return B < 0 ? 0 : 4 * sstem::FLOW_MAXRAD_PARTS * B; }
+
+int sstem_flow_color_u8(const float* flow, int64_t B, int64_t H, int64_t W, int hwc, uint8_t* rgb, void* workspace, void* stream)
+{
+    const char* what = "flow colour";
+    bool done;
+    const int rc = display_checks(what, B, H, W, &done);
+    if (rc != SSTEM_OK || done) return rc;
+    if (!flow || !rgb || !workspace) return fail(SSTEM_ERR_NULL_POINTER, "%s: null flow, rgb or workspace", what);
+    if (reinterpret_cast<uintptr_t>(workspace) & 7) return fail(SSTEM_ERR_UNSUPPORTED, "%s: the workspace must be 8-byte aligned", what);
+    return launched(what, sstem::launch_flow_color(flow, (int)B, H * W, hwc ? 1 : 0, rgb, static_cast<unsigned*>(workspace),
+                                                   static_cast<hipStream_t>(stream)), " launch");
+}
+
+int sstem_sff_outputs_u8(const float* pred, const float* warped, const uint8_t* interp, int64_t B, int64_t H, int64_t W,
+                         uint8_t* pred_u8, uint8_t* warped_rgb, uint8_t* stitch_u8, void* stream)
+{
+    const char* what = "sff outputs";
+    bool done;
+    const int rc = display_checks(what, B, H, W, &done);
+    if (rc != SSTEM_OK || done) return rc;
+    if (pred_u8 && !pred) return fail(SSTEM_ERR_NULL_POINTER, "%s: pred_u8 needs pred", what);
+    if (warped_rgb && !warped) return fail(SSTEM_ERR_NULL_POINTER, "%s: warped_rgb needs warped", what);
+    if (stitch_u8 && (!warped || !interp)) return fail(SSTEM_ERR_NULL_POINTER, "%s: stitch_u8 needs warped and interp", what);
+    if (!pred_u8 && !warped_rgb && !stitch_u8) return SSTEM_OK;
+    return launched(what, sstem::launch_sff_outputs(pred, warped, interp, (int)B, H * W, pred_u8, warped_rgb, stitch_u8,
+                                                    static_cast<hipStream_t>(stream)), " launch");
 }
 
 }  // extern "C"

@@ -20,6 +20,7 @@ import sstem_native
 from model.model_fusionnet import FusionNet
 from model.model_interp import IFNet
 from model.model_unet import UNet
+from utils.flow_display import flow_color_batch
 from utils.image_warp_torch import SpatialTransformation
 
 _warp = SpatialTransformation(use_gpu=True)
@@ -71,6 +72,44 @@ def restore_sff(models, prev, nxt, sff, quantise_interp=False):
     interp = interpolate(models, prev, nxt, quantise_interp)
     pred, flow, warped = fuse(models, sff, interp)
     return pred, interp, flow, warped
+
+
+def _planes(t, name, channels, dtype):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise NotImplementedError("sff_pipeline.outputs is GPU-only: %s must be a GPU tensor" % name)
+    if t.dtype != dtype:
+        raise TypeError("sff_pipeline.outputs: %s must be %s (got %s)" % (name, dtype, t.dtype))
+    if channels == 1 and t.dim() == 4 and t.shape[1] == 1:
+        t = t[:, 0]
+    if t.dim() != (3 if channels == 1 else 4) or (channels != 1 and t.shape[1] != channels):
+        raise ValueError("sff_pipeline.outputs: %s has shape %r" % (name, tuple(t.shape)))
+    return t.contiguous()
+
+
+@torch.no_grad()
+def outputs(pred, warped, interp_u8, flow=None):
+    """The images the two inference scripts save (sff_scripts_fusion/inference.py:161-172, sff_scripts_unfolding/inference.py:146-153),
+    made on the device (``include/sstem_display.h``): one launch for the images, two for the flow.
+    pred [B,1,H,W] or [B,H,W] and warped [B,3,H,W] float32 as ``fuse`` returns them, interp_u8 [B,H,W] or [B,1,H,W] uint8 -- the
+    interpolated section as the script read it from its file.  Returns
+    (pred_u8 [B,H,W], warped_rgb [B,H,W,3], stitch [B,H,W]) uint8, and as a fourth the colour image [B,H,W,3] of flow [B,2,H,W] when
+    it is given.  pad: 0, as in every shipped configuration.  Nothing synchronises."""
+    pred, warped, interp_u8 = _planes(pred, "pred", 1, torch.float32), _planes(warped, "warped", 3, torch.float32), _planes(interp_u8, "interp_u8", 1, torch.uint8)
+    B, H, W = pred.shape
+    if warped.shape != (B, 3, H, W) or interp_u8.shape != (B, H, W) or warped.device != pred.device or interp_u8.device != pred.device:
+        raise ValueError("sff_pipeline.outputs: pred %r, warped %r and interp_u8 %r do not belong together"
+                         % (tuple(pred.shape), tuple(warped.shape), tuple(interp_u8.shape)))
+    pred_u8 = torch.empty((B, H, W), dtype=torch.uint8, device=pred.device)
+    warped_rgb = torch.empty((B, H, W, 3), dtype=torch.uint8, device=pred.device)
+    stitch = torch.empty((B, H, W), dtype=torch.uint8, device=pred.device)
+    lib = sstem_native.load_library()
+    with torch.cuda.device(pred.device):
+        rc = lib.sstem_sff_outputs_u8(pred.data_ptr(), warped.data_ptr(), interp_u8.data_ptr(), B, H, W, pred_u8.data_ptr(),
+                                      warped_rgb.data_ptr(), stitch.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    sstem_native.check(rc, "sstem_sff_outputs_u8")
+    if flow is None:
+        return pred_u8, warped_rgb, stitch
+    return pred_u8, warped_rgb, stitch, flow_color_batch(flow)
 
 
 def restore_sharded(models, tiles, rank, world):

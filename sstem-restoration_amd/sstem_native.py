@@ -1,5 +1,5 @@
 """Single loader of ``csrc/libsstem_hip.so`` and the ctypes prototypes of its whole C-ABI
-(``include/sstem_sepconv.h``, ``include/sstem_conv.h``, ``include/sstem_warp.h``, ``include/sstem_resize.h``, ``include/sstem_norm.h``, ``include/sstem_io.h``, ``include/sstem_loss.h``, ``include/sstem_score.h``, ``include/sstem_fold.h``, ``include/sstem_jitter.h``, ``include/sstem_batch.h``).  No fallback: a missing library raises."""
+(``include/sstem_sepconv.h``, ``include/sstem_conv.h``, ``include/sstem_warp.h``, ``include/sstem_resize.h``, ``include/sstem_norm.h``, ``include/sstem_io.h``, ``include/sstem_loss.h``, ``include/sstem_score.h``, ``include/sstem_fold.h``, ``include/sstem_jitter.h``, ``include/sstem_batch.h``, ``include/sstem_display.h``).  No fallback: a missing library raises."""
 import ctypes
 import os
 
@@ -131,6 +131,11 @@ C_ABI = {
     # include/sstem_batch.h
     "sstem_crop_orient_u8": (_int, [_p, _p, _i64, _p, _p] + [_i64] * 4 + [_p, _p]),
     "sstem_crop_orient_f32": (_int, [_p, _p, _i64, _p, _p] + [_i64] * 4 + [_p, _i64, _i64, ctypes.c_uint32, _p, _p, _p]),
+    # include/sstem_display.h
+    "sstem_flow_color_wheel": (ctypes.POINTER(ctypes.c_uint8), []),
+    "sstem_flow_color_workspace_bytes": (_i64, [_i64]),
+    "sstem_flow_color_u8": (_int, [_p] + [_i64] * 3 + [_int] + [_p] * 3),
+    "sstem_sff_outputs_u8": (_int, [_p] * 3 + [_i64] * 3 + [_p] * 4),
 }
 
 
