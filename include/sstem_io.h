@@ -18,6 +18,11 @@
  *                                   target| and grad = sign(pred - target) / n (sign(0) = 0) in ONE launch, deterministic
  *                                   (fixed-order sums).  workspace: sstem_l1_workspace_floats() floats, zero before the first
  *                                   call, reusable afterwards without another fill (the launch leaves it clean), one per stream.
+ * sstem_l2_mean_forward_grad_f32  replaces  F.mse_loss(pred, target) + its backward (cfg.TRAIN.loss = 'L2': sff_scripts_interp/main_ms.py,
+ *                                   sff_scripts_fusion/main_fusion.py, sff_scripts_unfolding/main_flowfusionnet.py): *loss = mean (pred -
+ *                                   target)^2 and grad = fl32(fl32(2 / n) * fl32(pred - target)) in ONE launch.  The L1 entry's twin: the
+ *                                   same workspace (sstem_l1_workspace_floats()), refusals, determinism and scalar path for views that are
+ *                                   not 16-byte aligned.
  * Device pointers; same status codes / stream / ownership rules as sstem_sepconv.h.
  */
 #ifndef SSTEM_IO_H
@@ -36,6 +41,8 @@ int sstem_adam_step_f32(float* param, const float* grad, float* exp_avg, float* 
                         void* stream);
 int64_t sstem_l1_workspace_floats(void);
 int sstem_l1_mean_forward_grad_f32(const float* pred, const float* target, int64_t n, float* loss, float* grad, float* workspace,
+                                   void* stream);
+int sstem_l2_mean_forward_grad_f32(const float* pred, const float* target, int64_t n, float* loss, float* grad, float* workspace,
                                    void* stream);
 
 #ifdef __cplusplus

@@ -637,12 +637,71 @@ __global__ __launch_bounds__(256) void l1_mean_fwd_grad(const float* __restrict_
     }
 }
 
-hipError_t launch_l1_mean_fwd_grad(const float* pred, const float* target, int64_t n, float* loss, float* grad, float* ws, hipStream_t s)
+static inline unsigned l1_grid(int64_t n)
 {
     int64_t g = (n + 1023) / 1024;          // a thread handles one float4 per trip
     if (g > L1_MAX_WGS) g = L1_MAX_WGS;
     if (g < 1) g = 1;
-    hipLaunchKernelGGL(l1_mean_fwd_grad, dim3((unsigned)g), dim3(256), 0, s, pred, target, n, 1.0f / (float)n, loss, grad, ws);
+    return (unsigned)g;
+}
+
+hipError_t launch_l1_mean_fwd_grad(const float* pred, const float* target, int64_t n, float* loss, float* grad, float* ws, hipStream_t s)
+{
+    hipLaunchKernelGGL(l1_mean_fwd_grad, dim3(l1_grid(n)), dim3(256), 0, s, pred, target, n, 1.0f / (float)n, loss, grad, ws);
+    return hipGetLastError();
+}
+
+// ---- L2 loss, forward and gradient in ONE launch: the L1 launch's twin -----------------------------------------------------------
+// loss = mean (pred - target)^2 (F.mse_loss, cfg.TRAIN.loss = 'L2' of the three SFF loops) and grad = d loss / d pred =
+// fl32(fl32(2 / n) * fl32(pred - target)): the same grid, vector / scalar paths, workspace and last-arriver sum as l1_mean_fwd_grad.
+__global__ __launch_bounds__(256) void l2_mean_fwd_grad(const float* __restrict__ pred, const float* __restrict__ target, int64_t n,
+                                                         float inv_n, float two_inv_n, float* __restrict__ loss, float* __restrict__ grad,
+                                                         float* __restrict__ ws)
+{
+    __shared__ float red[4][1];
+    float acc = 0.f;
+    const int64_t n4 = n >> 2;
+    const bool vec = ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(grad)) & 15) == 0;
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    if (vec) {
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+            const f4 a = reinterpret_cast<const f4*>(pred)[i], b = reinterpret_cast<const f4*>(target)[i];
+            f4 g;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float d = a[e] - b[e];
+                acc = fmaf(d, d, acc);
+                g[e] = two_inv_n * d;
+            }
+            reinterpret_cast<f4*>(grad)[i] = g;
+        }
+    }
+    for (int64_t i = (vec ? n4 * 4 : 0) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float d = pred[i] - target[i];
+        acc = fmaf(d, d, acc);
+        grad[i] = two_inv_n * d;
+    }
+    const float sums[1] = {acc};
+    block_sum(sums, red);
+    unsigned* counter = reinterpret_cast<unsigned*>(ws + L1_MAX_WGS);
+    if (threadIdx.x == 0) agent_store(ws + blockIdx.x, block_tree(red, 0));
+    if (!arrive_last(counter)) return;
+    // the last workgroup: partials in index order, four per thread, then the fixed tree
+    float t[1] = {0.f};
+    for (int i = threadIdx.x * 4; i < (int)gridDim.x; i += 1024)
+        for (int e = 0; e < 4 && i + e < (int)gridDim.x; ++e) t[0] += agent_load(ws + i + e);
+    __syncthreads();
+    block_sum(t, red);
+    if (threadIdx.x == 0) {
+        *loss = block_tree(red, 0) * inv_n;
+        release_counter(counter);
+    }
+}
+
+hipError_t launch_l2_mean_fwd_grad(const float* pred, const float* target, int64_t n, float* loss, float* grad, float* ws, hipStream_t s)
+{
+    hipLaunchKernelGGL(l2_mean_fwd_grad, dim3(l1_grid(n)), dim3(256), 0, s, pred, target, n, 1.0f / (float)n, (float)(2.0 / (double)n), loss,
+                       grad, ws);
     return hipGetLastError();
 }
 

@@ -20,6 +20,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "ssim_blur.h"
 #include "ssim_kernels.h"
 #include "wg_reduce.h"
 
@@ -36,27 +37,12 @@ constexpr int BE = BM + HALO;                   // backward: staged image extent
 // workspace header (float slots)
 constexpr int HDR_VALUE = 0, HDR_TERMS = 2, HDR_COEF = 12, HDR_COUNTER = 20, HDR_IMG1 = 26, HDR_DTERMS = 32;
 
-struct Taps { float g[SSIM_TAPS]; };
+static_assert(SSIM_TAPS == SSIM_BLUR_TAPS, "one window length");     // Taps, stage_pair, make_taps: ssim_blur.h
 struct Counts { double inv[SSIM_MAX_LEVELS]; };     // 1 / (B oh ow) per level
 
 __device__ __forceinline__ float weight_of(int i)
 {
     return i == 0 ? 0.0448f : i == 1 ? 0.2856f : i == 2 ? 0.3001f : i == 3 ? 0.2363f : 0.1333f;
-}
-
-// E x E window of images x, y (h x w at `base`) from (y0, x0) into sx, sy; zero outside the image.
-template <int E>
-__device__ __forceinline__ void stage_pair(const float* __restrict__ x, const float* __restrict__ y, int64_t base, int h, int w, int y0,
-                                           int x0, float* sx, float* sy)
-{
-    for (int e = threadIdx.x; e < E * E; e += 256) {
-        const int r = e / E, c = e - r * E;
-        const int iy = y0 + r, ix = x0 + c;
-        const bool in = iy >= 0 && iy < h && ix >= 0 && ix < w;
-        const int64_t o = base + (int64_t)iy * w + ix;
-        sx[e] = in ? x[o] : 0.f;
-        sy[e] = in ? y[o] : 0.f;
-    }
 }
 
 // Forward of one level.  Workgroup = one 32 x 32 tile of one image's map (even origin, so it owns whole 2 x 2 pooling windows).
@@ -283,22 +269,6 @@ __global__ __launch_bounds__(256) void ms_ssim_level_bwd(const float* __restrict
             gout[base + (int64_t)jy * w + jx] = gr;
         }
     }
-}
-
-Taps make_taps(int ws)
-{
-    // gaussian() of loss_ssim.py:8-10: double exponentials rounded to fp32, divided by their fp32 sum, sigma following the window --
-    // not score_kernels.hip's make_taps, which is scipy's float64 window at a fixed sigma
-    Taps t;
-    const double sigma = 1.5 * ws / 11;
-    float f[SSIM_TAPS], sum = 0.f;
-    for (int k = 0; k < ws; ++k) {
-        const double d = (double)(k - ws / 2);
-        f[k] = (float)exp(-(d * d) / (2 * sigma * sigma));
-        sum += f[k];
-    }
-    for (int k = 0; k < SSIM_TAPS; ++k) t.g[k] = k < ws ? f[k] / sum : 0.f;
-    return t;
 }
 
 }  // namespace

@@ -23,6 +23,7 @@
 #include "misc_kernels.h"
 #include "norm_kernels.h"
 #include "ssim_kernels.h"
+#include "ssim_loss_kernels.h"
 #include "score_kernels.h"
 #include "fold_kernels.h"
 #include "jitter_kernels.h"
@@ -1406,6 +1407,15 @@ int sstem_l1_mean_forward_grad_f32(const float* pred, const float* target, int64
     return launched("l1 launch", e);
 }
 
+int sstem_l2_mean_forward_grad_f32(const float* pred, const float* target, int64_t n, float* loss, float* grad, float* workspace,
+                                   void* stream)
+{
+    if (n < 1 || n > ((int64_t)1 << 40)) return fail(SSTEM_ERR_BAD_SHAPE, "l2: bad size");
+    if (!pred || !target || !loss || !grad || !workspace) return fail(SSTEM_ERR_NULL_POINTER, "l2: null pointer");
+    hipError_t e = sstem::launch_l2_mean_fwd_grad(pred, target, n, loss, grad, workspace, static_cast<hipStream_t>(stream));
+    return launched("l2 launch", e);
+}
+
 // ---- MS-SSIM criterion (include/sstem_loss.h): both entries make the same checks, in this order, before any HIP call ----------------
 static int ms_ssim_checked(const char* what, bool any_null, int64_t B, int64_t H, int64_t W, int levels, float max_val, const float* workspace,
                            sstem::SsimPlan* plan, bool* empty)
@@ -1451,6 +1461,48 @@ int sstem_ms_ssim_backward_f32(const float* img1, const float* img2, int64_t B, 
     if (rc != SSTEM_OK || empty) return rc;
     hipError_t e = sstem::launch_ms_ssim_backward(img1, img2, B, plan, max_val, grad_value, grad_img1, workspace, static_cast<hipStream_t>(stream));
     return launched("ms_ssim backward launch", e);
+}
+
+// ---- single-scale SSIM criterion (include/sstem_loss.h): both entries make the same checks, in this order, before any HIP call ------
+static int ssim_loss_checked(const char* what, bool any_null, int64_t B, int64_t C, int64_t H, int64_t W, const float* workspace,
+                             sstem::SsimLossPlan* plan, bool* empty)
+{
+    *empty = false;
+    if (B < 0 || C < 0 || H < 0 || W < 0) return fail(SSTEM_ERR_BAD_SHAPE, "%s: negative size", what);
+    if (B == 0 || C == 0 || H == 0 || W == 0) { *empty = true; return SSTEM_OK; }
+    if (any_null) return fail(SSTEM_ERR_NULL_POINTER, "%s: null pointer", what);
+    if (!sstem::ssim_loss_plan(B, C, H, W, plan))
+        return fail(SSTEM_ERR_UNSUPPORTED, "%s: sizes past the index range (H, W <= 32768 and at most 2^24 tiles of 32 x 32)", what);
+    if (reinterpret_cast<uintptr_t>(workspace) & 7) return fail(SSTEM_ERR_UNSUPPORTED, "%s: the workspace must be 8-byte aligned", what);
+    return SSTEM_OK;
+}
+
+int64_t sstem_ssim_loss_workspace_floats(int64_t B, int64_t C, int64_t H, int64_t W)
+{
+    sstem::SsimLossPlan plan;
+    return sstem::ssim_loss_plan(B, C, H, W, &plan) ? plan.total_floats : 0;
+}
+
+int sstem_ssim_loss_forward_f32(const float* img1, const float* img2, int64_t B, int64_t C, int64_t H, int64_t W, int per_sample,
+                                float* value, float* workspace, void* stream)
+{
+    sstem::SsimLossPlan plan;
+    bool empty;
+    const int rc = ssim_loss_checked("ssim_loss forward", !img1 || !img2 || !value || !workspace, B, C, H, W, workspace, &plan, &empty);
+    if (rc != SSTEM_OK || empty) return rc;
+    hipError_t e = sstem::launch_ssim_loss_forward(img1, img2, B, plan, per_sample != 0, value, workspace, static_cast<hipStream_t>(stream));
+    return launched("ssim_loss forward launch", e);
+}
+
+int sstem_ssim_loss_backward_f32(const float* img1, const float* img2, int64_t B, int64_t C, int64_t H, int64_t W, int per_sample,
+                                 const float* grad_value, float* grad_img1, float* workspace, void* stream)
+{
+    sstem::SsimLossPlan plan;
+    bool empty;
+    const int rc = ssim_loss_checked("ssim_loss backward", !img1 || !img2 || !grad_img1 || !workspace, B, C, H, W, workspace, &plan, &empty);
+    if (rc != SSTEM_OK || empty) return rc;
+    hipError_t e = sstem::launch_ssim_loss_backward(img1, img2, B, plan, per_sample != 0, grad_value, grad_img1, static_cast<hipStream_t>(stream));
+    return launched("ssim_loss backward launch", e);
 }
 
 // ---- validation scores (include/sstem_score.h); the checks are score_checked, above --------------------------------------------

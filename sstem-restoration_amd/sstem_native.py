@@ -112,10 +112,14 @@ C_ABI = {
     "sstem_adam_step_f32": (_int, [_p] * 4 + [_i64] + [_f] * 5 + [_i64, _p]),
     "sstem_l1_workspace_floats": (_i64, []),
     "sstem_l1_mean_forward_grad_f32": (_int, [_p, _p, _i64, _p, _p, _p, _p]),
+    "sstem_l2_mean_forward_grad_f32": (_int, [_p, _p, _i64, _p, _p, _p, _p]),
     # include/sstem_loss.h
     "sstem_ms_ssim_workspace_floats": (_i64, [_i64] * 3 + [_int]),
     "sstem_ms_ssim_forward_f32": (_int, [_p, _p] + [_i64] * 3 + [_int, _f] + [_p] * 4),
     "sstem_ms_ssim_backward_f32": (_int, [_p, _p] + [_i64] * 3 + [_int, _f] + [_p] * 4),
+    "sstem_ssim_loss_workspace_floats": (_i64, [_i64] * 4),
+    "sstem_ssim_loss_forward_f32": (_int, [_p, _p] + [_i64] * 4 + [_int] + [_p] * 3),
+    "sstem_ssim_loss_backward_f32": (_int, [_p, _p] + [_i64] * 4 + [_int] + [_p] * 4),
     # include/sstem_score.h
     "sstem_score_workspace_bytes": (_i64, [_i64] * 3),
     "sstem_score_images_f32": (_int, [_p, _p] + [_i64] * 3 + [_int] + [_p] * 3),

@@ -8,6 +8,8 @@ Adam -- on synthetic ``torch.rand`` data; data providers and logging stay with t
                       UNet -> L1 -> backward -> all-reduce -> Adam(lr 1e-4)                       (BASELINE config 3)
 * ``IFNetStep``       sff_scripts_interp/main_ms.py:187-211: IFNet -> L1 -> backward -> all-reduce -> Adam(lr 1e-3)
                                                                                                   (BASELINE config 5)
+* ``UnfoldStep``      sff_scripts_unfolding/main_flowfusionnet.py:184-220: FusionNet(6, 2, 32) flow predictor -> L1 / L2 against the flow
+                      label -> backward -> all-reduce -> Adam(lr 1e-4)
 * ``SPJointStep``     sp_scripts_train/main_fusion.py:178-257: IFNet x2, UNet x2, FusionNet x2, six L1 losses, one
                       backward, three Adams
 * ``IFNetForward``    the whole interpolation forward on grayscale frame pairs (inference_singleImage.py:55-70)
@@ -81,6 +83,39 @@ class _TrainStep:
             self.loss = _l1(pred, target)
             self.loss.backward()
 
+    def _l2_backward(self, pred, target):
+        """loss="l2": F.mse_loss, as ``_loss_backward`` (train_utils.L2MeanLoss: one launch; SSTEM_NATIVE_L1=0: torch's mse_loss + backward)."""
+        if _NATIVE_L1:
+            self.loss, g = self.criterion(pred, target)
+            pred.backward(g)
+        else:
+            self.loss = torch.nn.functional.mse_loss(pred, target)
+            self.loss.backward()
+
+    def _ssim_loss_backward(self, pred, target):
+        """loss="ssim" of the interpolation loop: 1 - SSIM and the start of the backward pass at the network's output
+        (train_utils.SSIMMeanLoss; SSTEM_NATIVE_SSIM=0: loss.loss_ssim.ssim_loss_torch under autograd)."""
+        if self._native_ssim:
+            self.loss, g = self.criterion(pred, target)
+            pred.backward(g)
+        else:
+            self.loss = self.criterion(pred, target)
+            self.loss.backward()
+
+    def _set_criterion(self, device, loss):
+        """cfg.TRAIN.loss of the SFF interpolation and unfolding loops, for a name ``_check_loss_name`` has passed."""
+        self._l1 = train_utils.L1MeanLoss(device)
+        self.loss_name = loss
+        self.criterion = self._l1
+        if loss == "l2":
+            self.criterion = train_utils.L2MeanLoss(device)
+            self._loss_backward = self._l2_backward
+        elif loss == "ssim":
+            from loss.loss_ssim import ssim_loss_torch
+            self._native_ssim = _NATIVE_SSIM
+            self.criterion = train_utils.SSIMMeanLoss(device) if _NATIVE_SSIM else ssim_loss_torch
+            self._loss_backward = self._ssim_loss_backward
+
     def step(self):
         if self.reducer is not None:
             self.reducer.begin()
@@ -113,23 +148,31 @@ class _TrainStep:
     def bucket_bytes(self):
         return [bk.nbytes for bk in self.buckets]
 
-    def _validate(self, forward, gt):
+    def _validate(self, forward, gt, score=None):
         """The validation pass of the reference's loops (main_ms.py:250-279, main_fusion.py:309-355) for one batch: ``forward()`` with
         the trained net in eval mode under no_grad, then per image compute_psnr of the prediction clamped to [0, 1] against ``gt`` --
         [B] float64 on the device, from utils.psnr_ssim.score_batch(pred, gt, clamp01=True); nothing synchronises.  Eager, outside any
         captured graph; the step's batch buffers, its gradient bucket and the net's BatchNorm running statistics are not touched.
         Deliberate difference: the net is put back in the mode it was in (train); the reference leaves its model in eval mode after
         the first validation, so every later training step there normalises with the running statistics.  The reference's TPAD
-        padding of the input and cropping of the prediction stay with the caller, like its data providers."""
+        padding of the input and cropping of the prediction stay with the caller, like its data providers.
+        score: another validation number of (pred, gt) under the same mode handling (the unfolding loop's end-point error)."""
         from utils.psnr_ssim import score_batch
         was_training = self.net.training
         self.net.eval()
         try:
             with torch.no_grad():
                 pred = forward()
+                if score is not None:
+                    return score(pred, gt)
                 return score_batch(pred, gt, clamp01=True)[:, 1]
         finally:
             self.net.train(was_training)
+
+
+def _check_loss_name(loss, names):
+    if loss not in names:
+        raise AttributeError('No this loss function!')
 
 
 class FusionStep(_TrainStep):
@@ -272,7 +315,13 @@ class FusionStep(_TrainStep):
 class IFNetStep(_TrainStep):
     FWD_FLOP_PER_SAMPLE = 45.7e9        # SFF IFNet at 256x256
 
-    def __init__(self, device, global_batch=8, size=256, lr=1e-3, seed=555, graph=False, net=None):
+    def __init__(self, device, global_batch=8, size=256, lr=1e-3, seed=555, graph=False, net=None, loss="l1"):
+        """loss: the criterion, cfg.TRAIN.loss of the reference (main_ms.py:149-161).  "l1" (the default) is nn.L1Loss, "l2" is F.mse_loss
+        (train_utils.L2MeanLoss), "ssim" is SSIMLoss() = 1 - SSIM (train_utils.SSIMMeanLoss: value and gradient from native launches;
+        SSTEM_NATIVE_SSIM=0 selects the plain-torch formulation loss.loss_ssim.ssim_loss_torch for A/B runs).  With "ssim" the step descends
+        1 - SSIM, as main_ms.py:203-206 does: here the sign is the useful one.  Any other name raises AttributeError('No this loss
+        function!'), like :161."""
+        _check_loss_name(loss, ("l1", "l2", "ssim"))
         from model.model_interp import IFNet
         torch.manual_seed(seed)
         self.net = (net if net is not None else IFNet(51)).train().to(device)
@@ -287,7 +336,7 @@ class IFNetStep(_TrainStep):
         self.x = torch.cat((f[:, :1].expand(b, 3, size, size), f[:, 1:].expand(b, 3, size, size)), 1).contiguous()
         self.target = torch.rand(b, 1, size, size, device=device, generator=g)
         self.loss = None
-        self._l1 = train_utils.L1MeanLoss(device)
+        self._set_criterion(device, loss)
         self._finish_init(graph)
 
     def flop_per_step(self):
@@ -297,6 +346,51 @@ class IFNetStep(_TrainStep):
         """Per-image PSNR [B] of the eval-mode forward on x [B,6,H,W] against gt [B,1,H,W] (GPU tensors), as main_ms.py:260-266
         (see ``_validate``)."""
         return self._validate(lambda: self.net(x), gt)
+
+    def forward_backward(self):
+        self.buckets[0].zero()
+        self._loss_backward(self.net(self.x), self.target)
+
+
+class UnfoldStep(_TrainStep):
+    FWD_FLOP_PER_SAMPLE = FusionStep.FLOW_FWD_FLOP_PER_SAMPLE       # the flow FusionNet at 256x256 (SURVEY 8a a11)
+
+    def __init__(self, device, global_batch=32, size=256, lr=1e-4, seed=555, graph=False, net=None, loss="l1"):
+        """The unfolding loop's step (sff_scripts_unfolding/main_flowfusionnet.py:184-220): the flow predictor FusionNet(6, 2, 32) in train
+        mode on x [b,6,s,s] (the folded section and its neighbour, data.fold_degradation.FoldSynthesizer.batch(..., label="flow"))
+        against the flow label [b,2,s,s], in pixels.  loss: cfg.TRAIN.loss, "l1" (nn.L1Loss) or "l2" (F.mse_loss); the loop's
+        'ssim' (MS_SSIM, whose one-channel window refuses a two-channel flow) and 'perceptual' are not built here; any other name raises AttributeError('No this loss
+        function!'), like :182.  net: a prebuilt module instead of the seeded random one.  The step is what produces the "pretrained flow
+        predictor" FusionStep takes as ``flow=``."""
+        _check_loss_name(loss, ("l1", "l2"))
+        from model.model_fusionnet import FusionNet
+        torch.manual_seed(seed)
+        self.net = (net if net is not None else FusionNet(6, 2, 32)).train().to(device)
+        dp.broadcast_module(self.net)
+        self.modules = [self.net]
+        self.flat = train_utils.FlatParams(self.net.parameters())
+        self.buckets = [dp.FlatGradBucket(self.net.parameters())]
+        self.opts = [train_utils.FlatAdam(self.flat.flat, self.buckets[0].flat, lr=lr, betas=(0.9, 0.999), eps=1e-8)]
+        b = self.batch = _local_batch(global_batch)
+        g = torch.Generator(device=device); g.manual_seed(seed + 1000 * dp.rank())
+        self.x = torch.rand(b, 6, size, size, device=device, generator=g)
+        self.target = (torch.rand(b, 2, size, size, device=device, generator=g) - 0.5) * 8.0        # a few pixels either way
+        self.loss = None
+        self._set_criterion(device, loss)
+        self._finish_init(graph)
+
+    def flop_per_step(self):
+        return 3 * self.FWD_FLOP_PER_SAMPLE * self.batch * (self.x.shape[2] / 256.0) ** 2
+
+    def load(self, x, target):
+        """The batch the next ``step()`` trains on ([B,6,H,W] and the flow label [B,2,H,W], any device)."""
+        self.x.copy_(x); self.target.copy_(target)
+
+    def validate(self, x, gt):
+        """loss.multiscaleloss.EPE of the eval-mode forward on x [B,6,H,W] against the flow gt [B,2,H,W] (GPU tensors), a 0-d device
+        tensor: for images of one size the mean of the reference's per-image EPEs (main_flowfusionnet.py:270-279; see ``_validate``)."""
+        from loss.multiscaleloss import EPE
+        return self._validate(lambda: self.net(x), gt, score=EPE)
 
     def forward_backward(self):
         self.buckets[0].zero()

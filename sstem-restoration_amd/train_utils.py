@@ -122,6 +122,55 @@ class L1MeanLoss:
         return loss, grad.view(pred.shape)
 
 
+class L2MeanLoss:
+    """``loss, grad = L2MeanLoss(device)(pred, target)``: F.mse_loss(pred, target) (cfg.TRAIN.loss = 'L2' of the three SFF loops) AND
+    d loss / d pred = 2 (pred - target) / n, from ONE native launch (include/sstem_io.h, sstem_l2_mean_forward_grad_f32): the shape,
+    workspace and rules of ``L1MeanLoss``."""
+
+    def __init__(self, device):
+        self._lib = sstem_native.load_library()
+        self._check = sstem_native.check
+        self._ws = torch.zeros(int(self._lib.sstem_l1_workspace_floats()), dtype=torch.float32, device=device)
+
+    def __call__(self, pred, target):
+        if not (pred.is_cuda and target.is_cuda):
+            raise NotImplementedError("L2MeanLoss is GPU-only")
+        if pred.dtype != torch.float32 or target.dtype != torch.float32 or pred.shape != target.shape:
+            raise TypeError("L2MeanLoss: float32 tensors of one shape")
+        p = pred.detach().contiguous()
+        t = target.detach().contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=p.device)
+        grad = torch.empty_like(p)
+        with torch.cuda.device(p.device):
+            rc = self._lib.sstem_l2_mean_forward_grad_f32(p.data_ptr(), t.data_ptr(), p.numel(), loss.data_ptr(), grad.data_ptr(),
+                                                          self._ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        self._check(rc, "sstem_l2_mean_forward_grad_f32")
+        return loss, grad.view(pred.shape)
+
+
+class SSIMMeanLoss:
+    """``loss, grad = SSIMMeanLoss(device)(pred, target)``: the reference's ``SSIMLoss()(pred, target)`` = 1 - mean SSIM
+    (sff_scripts_interp/loss/loss_ssim.py:109-135, the criterion of cfg.TRAIN.loss = 'ssim': main_ms.py:153-155,203) AND d loss / d pred,
+    from two native launches (include/sstem_loss.h) -- the call shape of ``L1MeanLoss`` / ``MSSSIMLoss``.  ``[B,C,H,W]`` float32 GPU
+    tensors.  One object per call site and per stream: it owns the launches' workspace, which grows when a larger shape arrives --
+    outside graph capture, so run a shape once before capturing it."""
+
+    def __init__(self, device):
+        from loss import loss_ssim
+        self._m = loss_ssim
+        self._wsp = loss_ssim._SSIMLossWorkspace()
+        self.device = device
+
+    def __call__(self, pred, target):
+        m = self._m
+        m._check_ssim_loss_images(pred, target)
+        p = pred.detach().contiguous()
+        t = target.detach().contiguous()
+        loss, ws = m._ssim_loss_forward(self._wsp, p, t, False)
+        grad = m._ssim_loss_backward(self._wsp.lib, ws, p, t, False, None)
+        return loss, grad.view(pred.shape)
+
+
 class MSSSIMLoss:
     """``value, grad = MSSSIMLoss(device, max_val=1.0, levels=5)(pred, target)``: the reference's ``MS_SSIM(max_val)(pred, target)``
     (sff_scripts_fusion/loss/loss_ssim.py:18-72, the criterion of cfg.TRAIN.loss = 'ssim': main_fusion.py:198-199,252) AND
