@@ -31,11 +31,24 @@ populates a dropped product (``OutsideExactDomain``).
   bits); (B) swapped.  Two-piece x two-piece populates the dropped h1g1.  All values stay within 18 binades of the tensor's bound
   (the pieces then add up to the value, which exact_domain checks); the amax word is the true maximum.
 * **X3** (two bf16 pieces; kept: hh hm mh).  (A) input of at most 16 bits x weight of at most 8 bits; (B) swapped.
-* **BF16** (one piece): both operands at most 8 bits -- families A and B degenerate to one-piece x one-piece ("I").
+* **BF16** (one piece): both operands at most 8 bits -- families A and B degenerate to one-piece x one-piece ("I").  The id ROUNDS by
+  contract ("rounded to bf16 (RNE)", include/sstem_conv.h), so it has two more families whose dense operand needs rounding: (R) a
+  dense ``needs_rounding`` input x few-hot small-integer weights, (R') dense ``needs_rounding`` weights x an input that is few-hot
+  over pixels and channels.  ``exact_domain("bf16", x, w, rounded=True)`` accepts such a pair: the single piece IS the rounded
+  value ``rne_bf16(x)`` and the residual x - piece is dropped by contract, so the reference is the float64 convolution of the two
+  rounded operands and the budget is taken over the rounded magnitudes.  Without ``rounded`` a multi-piece operand is still refused.
 * **fp32 MFMA, DIRECT, streaming**: exact products, so any operand pair inside the budget: A, B and C.
 
 Generators
 ----------
+``needs_rounding`` draws  s (128 + k + f/4) 2^e  (k in 0..127, f in 0..3, e in -2..2): ten significant bits, of which bf16 keeps
+eight, so f selects the rounding class -- exact (f = 0), below half (1), a tie (2; to even: downwards in magnitude for k even, upwards
+for k odd), above half (3), and for k = 127, f >= 2 a carry into the next binade.  ``rounding_census`` counts the six classes from
+the bit patterns of any fp32 tensor and ``assert_rounding_census`` asks for at least 5 % in each of the first five and two carries
+per thousand elements: a randn value is never a tie, so a test on randn data cannot tell round-to-nearest-even from round-half-away
+or round-half-up.  ``rounding_store_operands`` makes 8-bit operands (nothing rounds while they are staged) whose SUMS need ten bits:
+what a bf16 output store has to round, with the same census asserted of the values before the store.
+
 Multi-piece values are  a + b 2^-8 + c 2^-19  (three bf16 pieces),  a + b 2^-8  (two) and  a + c 2^-shift, shift = 12  (two fp16
 pieces), a in +-{2, 3}, b and c in +-{1, 2, 3}: at most 21 significant bits.  Which pieces a value populates depends on where the
 roundings fall (c 2^-16 instead of c 2^-19 disappears into the second bf16 piece on two thirds of the elements), so ``multi_piece``
@@ -70,7 +83,97 @@ KEPT = {
     "bf16": ("bf16", 1, [(0, 0)]),
     "fp32": (None, 1, [(0, 0)]),
 }
-FAMILIES = {"x6": ("A", "B", "C"), "x3": ("A", "B"), "f16x3": ("A", "B"), "bf16": ("I",), "fp32": ("A", "B", "C")}
+FAMILIES = {"x6": ("A", "B", "C"), "x3": ("A", "B"), "f16x3": ("A", "B"), "bf16": ("I", "R", "R'"), "fp32": ("A", "B", "C")}
+ROUNDED_FAMILIES = ("R", "R'")                                   # the dense operand is not a bf16 number: the id rounds it (BF16 only)
+Q_ROUNDED = 2.0 ** -2                                            # quantum of a rounded needs_rounding value
+CENSUS_CLASSES = ("exact", "below_half", "tie_down", "tie_up", "above_half", "carry")
+
+
+# ---- round to nearest even, restated on the bit pattern ----------------------------------------------------------------------------------
+def _bits(x):
+    assert x.dtype == torch.float32
+    return x.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+
+
+def _from_bits(u):
+    u = torch.where(u >= 2 ** 31, u - 2 ** 32, u)
+    return u.to(torch.int32).view(torch.float32)
+
+
+def rne_bf16(x, mode="rne"):
+    """fp32 -> the nearest bf16 number, ties to even, as an fp32 tensor: add 0x7FFF + bit 16 to the bit pattern, clear the low half
+    (integer tensor operations only; a NaN stays a NaN).  It restates the contract of include/sstem_conv.h, not the kernel.  The other
+    modes are the MUTANTS of tests/test_conv_bf16_exact_cpu.py: "trunc" clears the low half, "away" adds 0x8000 (ties away from
+    zero), "up" rounds ties towards +infinity."""
+    u = _bits(x)
+    if mode == "rne":
+        r = u + 0x7FFF + ((u >> 16) & 1)
+    elif mode == "trunc":
+        r = u
+    elif mode == "away":
+        r = u + 0x8000
+    elif mode == "up":                                            # positive: half rounds up in magnitude; negative: half rounds down
+        r = u + torch.where((u >> 31) == 0, torch.full_like(u, 0x8000), torch.full_like(u, 0x7FFF))
+    else:
+        raise ValueError(mode)
+    r = r & 0xFFFF0000
+    nan = ((u & 0x7F800000) == 0x7F800000) & ((u & 0x007FFFFF) != 0)
+    r = torch.where(nan, (u & 0xFFFF0000) | 0x00400000, r)
+    return _from_bits(r).reshape(x.shape)
+
+
+def rounding_census(x):
+    """How many elements of the fp32 tensor fall into each class of the bf16 rounding (CENSUS_CLASSES), from the bit patterns: the
+    dropped half against 0x8000, bit 16 for the direction of a tie; a carry is a value that rounds UP out of an all-ones kept
+    mantissa (it is counted in its own class as well)."""
+    u = _bits(x)
+    low, odd, ones = u & 0xFFFF, ((u >> 16) & 1) == 1, ((u >> 16) & 0x7F) == 0x7F
+    tie = low == 0x8000
+    up = (low > 0x8000) | (tie & odd)
+    counts = [low == 0, (low > 0) & (low < 0x8000), tie & ~odd, tie & odd, low > 0x8000, up & ones]
+    return {k: int(c.sum()) for k, c in zip(CENSUS_CLASSES, counts)}
+
+
+def assert_rounding_census(census, n, what="tensor"):
+    """At least 5 % of the n elements in each of the first five classes and two carries per thousand: a condition on the INPUTS."""
+    for k in CENSUS_CLASSES[:5]:
+        assert census[k] >= 0.05 * n, "%s: only %d of %d elements are of the rounding class %s" % (what, census[k], n, k)
+    assert census["carry"] >= 0.002 * n and (n == 0 or census["carry"] >= 1), "%s: only %d carries in %d elements" % (what, census["carry"], n)
+    return census
+
+
+def needs_rounding(shape, gen, exps=(-2, -1, 0, 1, 2)):
+    """fp32 values  s (128 + k + f/4) 2^e,  k in 0..127, f in 0..3, e in `exps`, s = +-1, and the census of their six rounding classes,
+    which the function ASSERTS (assert_rounding_census) -- once from k and f, once from the bit patterns.  Carries (k = 127, f >= 2)
+    are two in 512 draws; where that leaves a tensor short of two per thousand (or of two at all), elements are planted.  The rounded
+    values are multiples of Q_ROUNDED 2^(2 + min e) and of magnitude <= 256 * 2^max(e)."""
+    n = 1
+    for d in shape:
+        n *= d
+    k = torch.randint(128, (n,), generator=gen)
+    f = torch.randint(4, (n,), generator=gen)
+    want = min(n, max(2, math.ceil(0.003 * n)))
+    short = want - int(((k == 127) & (f >= 2)).sum())
+    if short > 0:
+        at = torch.randperm(n, generator=gen)[:min(n, 2 * want)]
+        at = at[~((k[at] == 127) & (f[at] >= 2))][:short]
+        k[at] = 127
+        f[at] = 2 + torch.randint(2, (at.numel(),), generator=gen)
+    e = torch.tensor(list(exps), dtype=torch.float64)[torch.randint(len(exps), (n,), generator=gen)]
+    s = (torch.randint(2, (n,), generator=gen) * 2 - 1).double()
+    v = s * (128.0 + k.double() + f.double() / 4.0) * 2.0 ** e
+    x = v.float()
+    assert torch.equal(x.double(), v)
+    tie = f == 2
+    planned = {"exact": int((f == 0).sum()), "below_half": int((f == 1).sum()), "tie_down": int((tie & (k % 2 == 0)).sum()),
+               "tie_up": int((tie & (k % 2 == 1)).sum()), "above_half": int((f == 3).sum()), "carry": int(((k == 127) & (f >= 2)).sum())}
+    census = rounding_census(x)
+    assert census == planned, (census, planned)
+    assert_rounding_census(census, n, "needs_rounding")
+    r = rne_bf16(x)
+    assert_quantum(r, Q_ROUNDED * 2.0 ** (2 + min(exps)), "rounded value")
+    assert float(r.abs().max()) <= 256.0 * 2.0 ** max(exps) if n else True
+    return x.reshape(shape), census
 
 
 # ---- pieces, as torch's own casts make them --------------------------------------------------------------------------------------------
@@ -115,10 +218,21 @@ def pieces_of(algo_id, x, bound=None):
     return pieces_f16(x, bound) if kind == "f16" else pieces_bf16(x, P)
 
 
-def exact_domain(algo_id, x, w, x_bound=None, w_bound=None):
+def exact_domain(algo_id, x, w, x_bound=None, w_bound=None, rounded=False):
     """The pieces of both operands under `algo_id`, after checking that the id is exact on the pair: every operand is the sum of its
-    pieces, and of every dropped product at least one factor is zero everywhere.  Returns (x pieces, w pieces)."""
+    pieces, and of every dropped product at least one factor is zero everywhere.  Returns (x pieces, w pieces).
+    rounded (the "bf16" id only, families R and R'): the id rounds its operands by contract, so the single piece of each operand is
+    rne_bf16(operand) -- checked here to be what torch's own cast gives -- and the residual is dropped: the id is exact on the
+    ROUNDED pair, which is what the reference and the budget then take."""
     kind, P, kept = KEPT[algo_id]
+    if rounded:
+        if algo_id != "bf16":
+            raise OutsideExactDomain("%s does not round its operands by contract" % algo_id)
+        px, pw = [rne_bf16(x)], [rne_bf16(w)]
+        for name, t, ps in (("input", x, px), ("weight", w, pw)):
+            if not torch.equal(ps[0], t.bfloat16().float()):
+                raise OutsideExactDomain("bf16: the rounded %s is not torch's own bf16 cast" % name)
+        return px, pw
     px, pw = pieces_of(algo_id, x, x_bound), pieces_of(algo_id, w, w_bound)
     for name, t, ps in (("input", x, px), ("weight", w, pw)):
         if not torch.equal(sum(p.double() for p in ps), t.double()):
@@ -279,19 +393,69 @@ FAMILY_SPECS = {
     ("f16x3", "A"): ("f16x2", "ints", [(2.0, 1.0, 2.0, 1.0, 1.0, 2.0, 1.0, 1.0)], None),
     ("f16x3", "B"): ("int", "f16x2", None, 8),
     ("bf16", "I"): ("int", "ints", [(2.0, 1.0, 2.0, 1.0, 1.0, 2.0, 1.0, 1.0)], None),
+    # the rounded families: dense needs_rounding values (rounded: multiples of 2^-2, magnitude <= 1024) against six small integers per
+    # output sum: S <= 6 x 3 x 1024 + 3 = 2^16.2 q, far inside the budget
+    ("bf16", "R"): ("round", "ints", [(3.0, 1.0, 2.0, 1.0, 3.0, 2.0), (1.0, 2.0, 3.0, 1.0, 1.0, 2.0)], None),
+    ("bf16", "R'"): ("round", "ints", [(3.0, 1.0, 2.0, 1.0, 3.0, 2.0), (1.0, 2.0, 3.0, 1.0, 1.0, 2.0)], None),
 }
 for _f in ("A", "B", "C"):
     FAMILY_SPECS[("fp32", _f)] = FAMILY_SPECS[("x6", _f)]
 
 
-def family_operands(algo_id, family, dense_shape, nout, domain, seed, must_hit=None, pixels=None):
+def few_hot_input(shape, per_sum, gen, must_hit=None):
+    """An [N, C, H, W] input that is few-hot over pixels AND channels: about `per_sum` entries of +-{1, 2, 3} inside the 9 C values a
+    3 x 3 output sum reads, at random positions of every image (one of them inside `must_hit`, a bool tensor over (C, H, W)), and one
+    entry on every special_pixels position, walking through the channels from the last one down."""
+    N, C, H, W = shape
+    entries = min(C * H * W, max(1, math.ceil(per_sum * H * W / 9.0)))
+    x, _ = few_hot(N, (C, H, W), entries, gen, "ints", [float(1 + i % 3) for i in range(entries)], must_hit)
+    for i, (n, y, xx) in enumerate(special_pixels(N, H, W)):
+        x[n, C - 1 - i % C, y, xx] = float(1 + i % 3) * (1 - 2 * (i % 2))
+    return x
+
+
+def _rounded_family_operands(family, dense_shape, nout, domain, gen, seed, must_hit, pixels, exps):
+    mags = FAMILY_SPECS[("bf16", family)][2]
+    m = list(mags[seed % len(mags)])
+    if pixels is not None:                                        # weight gradient: (input, gradient [N, nout, H, W])
+        N, H, W = pixels
+        m = m[:N * H * W]
+        def on_every_special_pixel(hot):                          # (few_hot_pixels reaches two of them per channel: too few with 8 channels)
+            for i, (n, y, xx) in enumerate(special_pixels(N, H, W)):
+                hot[n, i % hot.shape[1], y, xx] = float(1 + i % 3) * (1 - 2 * (i % 2))
+            return hot
+        if family == "R":
+            dense, _ = needs_rounding(dense_shape, gen, exps)
+            hot, _ = few_hot_pixels(nout, N, H, W, len(m), gen, "ints", m)
+            return dense, on_every_special_pixel(hot), Q_ROUNDED
+        dense, _ = needs_rounding((N, nout, H, W), gen, exps)
+        hot, _ = few_hot_pixels(dense_shape[1], N, H, W, len(m), gen, "ints", m)
+        return on_every_special_pixel(hot), dense, Q_ROUNDED
+    if family == "R":
+        dense, _ = needs_rounding(dense_shape, gen, exps)
+        room = int(torch.tensor(domain).prod())
+        hot, _ = few_hot(nout, domain, min(len(m), room), gen, "ints", m[:room], must_hit)
+        return dense, hot, Q_ROUNDED
+    dense, _ = needs_rounding((nout,) + tuple(domain), gen, exps)
+    chan = None
+    if must_hit is not None:                                      # must_hit is over the weights' (Cin, 3, 3): the same channels of the input
+        chan = must_hit.reshape(must_hit.shape[0], -1).any(1).view(-1, 1, 1).expand(dense_shape[1:]).contiguous()
+    return few_hot_input(dense_shape, len(m), gen, chan), dense, Q_ROUNDED
+
+
+def family_operands(algo_id, family, dense_shape, nout, domain, seed, must_hit=None, pixels=None, exps=(-2, -1, 0, 1, 2)):
     """One operand pair of `family` under `algo_id`: (dense, few_hot, q).  The dense operand has `dense_shape`; the few-hot one is
     [nout, *domain] (weights: domain = (Cin, 3, 3)), or [N, nout, H, W] gradient pixels when pixels = (N, H, W).  In families A, C
-    and I the dense operand is the multi-piece one; in B the few-hot one is."""
+    and I the dense operand is the multi-piece one; in B the few-hot one is.
+    The rounded families of the "bf16" id return (input-side operand [dense_shape], weight-side operand, Q_ROUNDED): under R the
+    input is the dense needs_rounding one (exponents `exps`) and the other few-hot small integers; under R' the weight-side operand
+    ([nout, *domain], or the [N, nout, H, W] gradient) is dense and the input few-hot (few_hot_input / few_hot_pixels)."""
     if family not in FAMILIES[algo_id]:
         raise OutsideExactDomain("%s is not exact on family %s" % (algo_id, family))
     dk, fk, mags, entries = FAMILY_SPECS[(algo_id, family)]
     gen = torch.Generator().manual_seed(seed)
+    if family in ROUNDED_FAMILIES:
+        return _rounded_family_operands(family, dense_shape, nout, domain, gen, seed, must_hit, pixels, exps)
     dense, qd = multi_piece(dense_shape, dk, gen)
     room = pixels[0] * pixels[1] * pixels[2] if pixels is not None else int(torch.tensor(domain).prod())
     if mags is not None:
@@ -453,3 +617,49 @@ def forward_terms_abs(px, pw, bias=None, scale=None, shift=None, residual=None, 
     if residual is not None:
         S = S + residual.double().abs()
     return S
+
+
+# ---- operands for the bf16 OUTPUT store ----------------------------------------------------------------------------------------------------
+# the second (and third) weight of an output channel is its first one times 2^-j, j walking through this list: two channels in three
+# put the sum on the quarter grid of its last kept bit (where the ties are), the others put it anywhere between
+STORE_SHIFTS = (1, 2, 9, 1, 2, 5, 2, 1, 7, 2, 3, 1, 2, 4, 1, 2, 6, 2, 1, 8)
+Q_STORE = 2.0 ** -9
+
+
+def rounding_store_operands(shape, seed, act=2, slope=0.25, tries=24, with_scale=True):
+    """Operands whose EXACT fp32 result needs more than 8 significant bits, so that a bf16 output store has something to round, while
+    nothing rounds on the way in: inputs +-(128 + k) (8 bits; k = 127 on one element in twenty more than by chance, for the carries),
+    two-hot (even channels) or three-hot weights +-1, +-2^-j, +-2^-j' (STORE_SHIFTS), a bias on the grid 2^-2, 2^-3 or 2^-4, a scale
+    in {0.5, 1, 2} (None without `with_scale`).  Returns (x, w, bias, scale, pre, census): `pre` is epilogue_ref64 of the float64 convolution -- the value BEFORE
+    the store, every stage an fp32 number --, and the reference of the stored tensor is rne_bf16(pre.float()).  The census of `pre`
+    is asserted (assert_rounding_census); seed and bias grid are stepped until it holds."""
+    N, Cin, H, W, Cout = shape
+    last = None
+    for t in range(tries):
+        gen = torch.Generator().manual_seed(seed + 1009 * t)
+        k = torch.randint(128, (N, Cin, H, W), generator=gen)
+        k = torch.where(torch.rand(N, Cin, H, W, generator=gen) < 1.0 / 20.0, torch.full_like(k, 127), k)
+        x = ((torch.randint(2, k.shape, generator=gen) * 2 - 1) * (128 + k)).float()
+        w = torch.zeros(Cout, Cin * 9)
+        for co in range(Cout):
+            pos = torch.randperm(Cin * 9, generator=gen)[:3 if co % 2 else 2]
+            j = (0, STORE_SHIFTS[(co + t) % len(STORE_SHIFTS)], STORE_SHIFTS[(co + t + 7) % len(STORE_SHIFTS)])
+            for i, p in enumerate(pos.tolist()):
+                w[co, p] = float(1 - 2 * int(torch.randint(2, (1,), generator=gen))) * 2.0 ** -j[i]
+        w = w.reshape(Cout, Cin, 3, 3)
+        grid = 2.0 ** -(2 + t % 3)
+        bias = (torch.randint(-8, 9, (Cout,), generator=gen).double() * grid).float()
+        scale = _pick((Cout,), [0.5, 1.0, 2.0], gen).float() if with_scale else None
+        for name, v in (("input", x), ("weight", w)):
+            assert torch.equal(rne_bf16(v), v), "%s: not a bf16 number" % name
+        assert_quantum(bias, Q_STORE, "bias")
+        assert_exactly_summable(forward_terms_abs([x], [w], bias), Q_STORE)
+        pre = epilogue_ref64(assert_fp32_number(conv_ref64(x, w, bias)), scale, None, act, slope)
+        census = rounding_census(pre.float())
+        try:
+            assert_rounding_census(census, pre.numel(), "values before the bf16 store")
+        except AssertionError as e:
+            last = e
+            continue
+        return x, w, bias, scale, pre, census
+    raise last

@@ -3,7 +3,10 @@
 Two references, both plain PyTorch on the CPU in fp64:
   * EXACT-OPERAND reference: the same op on inputs and weights rounded to bf16 first (torch's round-to-nearest-even).  Products
     of two bf16 values are exact in fp32, so the kernel may differ from this only by its fp32 summation order:
-    tolerance 2e-5 * max|ref| (the fp32 tests' bound).  This pins indexing, padding, packing and the rounding mode.
+    tolerance 2e-5 * max|ref| (the fp32 tests' bound).  This pins indexing, padding and packing on large elements, and rounding
+    as against truncation.  It does NOT pin the rounding mode on ties (a randn value is a tie once in 2^16 draws, so
+    round-half-away or round-half-up would pass), a single wrong element among small ones, or the bf16 tensors in absolute
+    terms: tests/test_conv_bf16_exact_gpu.py holds the id bit for bit on operands of every rounding class.
   * the un-rounded fp64 op: the bf16 id is allowed 2^-8 relative per operand; for sums of n products of random sign the
     observed error is ~2^-9 * sqrt(n) * typical product, tested as 1.5e-2 * max|ref| -- a sanity bound, not a parity claim.
 """
