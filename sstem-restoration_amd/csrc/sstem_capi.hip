@@ -1079,6 +1079,19 @@ int sstem_warp_bilinear_f32(const float* image, const float* flow, float* output
     return launched("warp launch", e);
 }
 
+int sstem_warp_bilinear_backward_f32(const float* image, const float* flow, const float* grad_output,
+                                     float* grad_flow, float* grad_image, int accumulate_image,
+                                     int64_t B, int64_t C, int64_t H, int64_t W, void* stream)
+{
+    if (!conv_sizes_ok(B, C, H, W, 2)) return fail(SSTEM_ERR_BAD_SHAPE, "warp backward: bad shape");
+    if (B == 0 || C == 0 || H == 0 || W == 0) return SSTEM_OK;
+    if (!flow || !grad_output || (!grad_flow && !grad_image) || (grad_flow && !image))
+        return fail(SSTEM_ERR_NULL_POINTER, "warp backward: null tensor pointer");
+    hipError_t e = sstem::launch_warp_bilinear_backward(image, flow, grad_output, grad_flow, grad_image, accumulate_image,
+                                                        (int)B, (int)C, (int)H, (int)W, static_cast<hipStream_t>(stream));
+    return launched("warp backward launch", e);
+}
+
 // ---- uint8 edge + flat Adam (include/sstem_io.h) -----------------------------------------------
 int sstem_gray_u8_to_f32(const uint8_t* image, float* output, int64_t npix, int64_t replicas, void* stream)
 {

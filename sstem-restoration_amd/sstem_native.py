@@ -93,6 +93,7 @@ C_ABI = {
     "sstem_conv_transpose3x3s2_backward_f32": (_int, [_p] * 5 + [_i64] * 5 + [_p]),
     # include/sstem_warp.h
     "sstem_warp_bilinear_f32": (_int, [_p] * 3 + [_i64] * 4 + [_p]),
+    "sstem_warp_bilinear_backward_f32": (_int, [_p] * 5 + [_int] + [_i64] * 4 + [_p]),
     # include/sstem_norm.h
     "sstem_batchnorm_workspace_floats": (_i64, [_i64] * 3),
     "sstem_batchnorm_train_forward_f32": (_int, [_p] * 9 + [_i64] + [_i64] * 3 + [_f, _f, _int, _f, _p]),
