@@ -156,6 +156,15 @@ int sstem_conv3x3_backward_weight_masked_f32(const float* input, const float* gr
  * raise slots (atomic max): sstem_amax_f32 makes one pass over a tensor; the split kernels add the largest value they STORE when given
  * output_amax (after bias, folded BatchNorm, activation and residual), so a chain of layers needs no extra pass.  A bound that is too
  * large costs precision only beyond 18 binades; a bound that is too small overflows fp16 -- never reuse a word for another tensor.
+ * Exactly: the consumer's scale 2^(141 - e), e the bound's biased exponent, puts the bound into [2^14, 2^15) and fp16 ends at 65504, so a
+ * tensor may exceed its word by any factor below 65504 / 2^15 = 1.999 before anything overflows.  The words the launches of this
+ * library write are exact (the largest magnitude stored, bit for bit).  A word that is HANDED ON by rule is not always: hipnn gives the
+ * input's word to a bilinearly up-sampled tensor, whose float32 interpolation (three roundings per axis) can exceed the largest input
+ * by up to 7 * 2^-24 of it (counted in tests/amax_audit.py; 3.9 * 2^-24 is the largest excess found over planes up to 64 x 64) -- inside
+ * that room by seven orders of magnitude.  Every finite bound is taken as it is (no upper clamp: 2^(141 - 254) is a normal float);
+ * bounds below 2^-111 scale by 2^125 (precision fades, nothing overflows); a non-finite bound means scale 1.  sstem_amax_f32 SKIPS
+ * NaNs (fmaxf returns its other operand): the word holds the largest magnitude among the other elements; an infinity gives an
+ * infinite bound.
  * sstem_conv3x3_forward_scaled_f32 = the 3x3 launch of sstem_conv2d_forward_ex_f32 (same weight flags, workspace rules -- sized by
  * sstem_conv3x3_forward_workspace_floats_algo --, residual store) for the ids SSTEM_CONV_MFMA_F16X3 (input_amax required), _BF16X6,
  * _BF16X3 (input_amax ignored), with the optional output bound and the output layout (SSTEM_LAYOUT_*).  The reference's blocks it serves: every Conv3x3 [+ BatchNorm eval]

@@ -198,7 +198,8 @@ _BF16_IO = os.environ.get("SSTEM_BF16_IO", "1") != "0"        # developer knob (
 # launch; a pool allocated while a HIP graph is being captured belongs to that capture (its fill is a node of the graph, so every
 # replay starts from zero again) -- pools are never shared between captures or between captured and eager launches.
 # A tensor carries its word as ``t._sstem_amax = (word, t._version, capture generation)``: an in-place edit of the tensor makes the pair stale and the
-# next consumer measures the tensor itself (one pass).  2 x 2 pooling and bilinear up-sampling hand the word on (convex combinations).
+# next consumer measures the tensor itself (one pass).  2 x 2 pooling and bilinear up-sampling hand the word on (convex combinations;
+# the up-sampling's float32 roundings can exceed the bound by 7 * 2^-24 of it, far inside the room the fp16 scale leaves: sstem_conv.h).
 _AMAX_FLOATS = 1024
 _AMAX_POOL_WORDS = 256
 _amax_pools = {}           # (device, capture generation or None) -> [pool tensor, next index]
@@ -218,8 +219,14 @@ def _new_amax_word(device):
     return w
 
 
+def _capturing():
+    """Is a HIP graph being captured on the current stream?  (False without asking the runtime while torch has not initialised a
+    device: the tag rules below also run on CPU tensors, on machines without a GPU.)"""
+    return torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
+
+
 def _capture_gen():
-    return capture_generation if torch.cuda.is_current_stream_capturing() else None
+    return capture_generation if _capturing() else None
 
 
 def tag_amax(t, word):
@@ -236,7 +243,7 @@ def amax_word_of(t):
     if tag is None and t._base is not None:      # a view (slice, narrow, reshape) holds a subset of its base's elements: the base's bound holds
         tag = getattr(t._base, "_sstem_amax", None)          # (views share their base's version counter)
     if tag is not None and tag[1] == t._version and tag[0].device == t.device:
-        if torch.cuda.is_current_stream_capturing() and tag[2] != capture_generation:
+        if _capturing() and tag[2] != capture_generation:
             return None
         return tag[0]
     return None
@@ -271,9 +278,13 @@ def hand_on_amax(src, dst):
 
 
 def measured_amax_word(x):
-    """x's amax word; measured by one pass over x (sstem_amax_f32) when no producer has bounded it."""
+    """x's amax word; measured by one pass over x (sstem_amax_f32) when no producer has bounded it.  The pass reads x.numel() floats
+    from x.data_ptr(): a view whose elements are not exactly those (a channel slice, a strided selection) is refused -- every caller
+    here passes what _check returned."""
     w = amax_word_of(x)
     if w is None:
+        if not x.is_contiguous():
+            raise ValueError("measured_amax_word: the measuring pass needs a contiguous tensor (shape %s, strides %s)" % (tuple(x.shape), x.stride()))
         w = _new_amax_word(x.device)
         with _on(x.device):
             rc = sstem_native.load_library().sstem_amax_f32(x.data_ptr(), x.numel(), w.data_ptr(), _stream())
@@ -1682,7 +1693,8 @@ class _UpsampleBilinear2x(torch.autograd.Function):
         with _on(g.device):
             rc = lib.sstem_upsample_bilinear2x_backward_f32(g.data_ptr(), gin.data_ptr(), N * C, H, W, _stream())
         sstem_native.check(rc, "sstem_upsample_bilinear2x_backward_f32")
-        # a source pixel gathers at most 3 x 3 weights of at most 1 (align_corners, scale (H - 1) / (2H - 1) >= 1/3): 16 x g's bound holds
+        # a source pixel gathers at most 4 x 4 weights of at most 1 (align_corners, scale (H - 1) / (2H - 1) >= 1/3; their sum stays
+        # below 9: tests/test_amax_audit_cpu.py): 16 x g's bound holds
         w = amax_word_of(g)
         if w is not None:
             tag_amax(gin, w * 16.0)
@@ -1703,7 +1715,9 @@ def upsample_bilinear2x_module(m, x):
             and x.shape[2] * x.shape[3] <= NATIVE_UPSAMPLE_MAX_PIXELS:
         if torch.is_grad_enabled() and x.requires_grad:
             return hand_on_amax(x, _UpsampleBilinear2x.apply(x))
-        return hand_on_amax(x, upsample_bilinear2x(x))      # interpolation weights are convex: x's bound holds
+        # interpolation weights are convex: x's bound holds -- to 7 * 2^-24 of it in float32, which the consumer's scale leaves room for
+        # (include/sstem_conv.h, "Amax words")
+        return hand_on_amax(x, upsample_bilinear2x(x))
     return m(x)
 
 

@@ -131,6 +131,52 @@ def upsample2x_backward_ref64(g, H, W):
     return ref, S
 
 
+# The float32 TWIN of the forward contract: not a reference to compare within a bound, but the kernels' own rounded operations, one by
+# one, on the CPU -- lerp2(w0, a, w1, b) = fma(w1, b, rn(w0 a)) with w0 = rn(1 - w1), horizontal first (csrc/misc_kernels.hip; the
+# three forward kernels share lerp2, so this is what all of them compute, bit for bit).  It is what answers "can an up-sampled value
+# exceed the largest input?" (tests/test_amax_audit_cpu.py): the float64 reference above shows the weights' own excess only (l0 + l1 is
+# at most 1 + 2^-25 per axis), not the three roundings of each lerp2.
+# Every operation is made in float64 on float32 values and rounded to float32 ONCE: a product of two float32 numbers is exact in
+# float64 (48 bits); the fma's sum is rounded to odd in float64 (TwoSum gives the exact error) before the rounding to float32, which
+# makes the double rounding the single one (53 >= 24 + 2).
+
+def _rn32(v):
+    import numpy as np
+    return v.astype(np.float32).astype(np.float64)
+
+
+def fma32(a, b, c):
+    """float32(a * b + c), rounded once, for float64 arrays that hold float32 values."""
+    import numpy as np
+    t = a * b                                                    # exact
+    s = t + c
+    bb = s - t
+    e = (t - (s - bb)) + (c - bb)                                # TwoSum: t + c = s + e exactly
+    fix = (e != 0) & ((s.view(np.int64) & 1) == 0)               # inexact and even: the odd neighbour lies towards e
+    s = np.where(fix, np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)
+    return _rn32(s)
+
+
+def lerp2_32(w0, a, w1, b):
+    return fma32(w1, b, _rn32(w0 * a))
+
+
+def upsample2x_twin32(x):
+    """x [..., H, W] float32 numpy array -> [..., 2H, 2W] float32: the forward kernels' arithmetic, operation by operation."""
+    import numpy as np
+    assert x.dtype == np.float32
+    H, W = x.shape[-2:]
+    y0, y1, l0y, l1y = [t.numpy() for t in axis_coords(H)]
+    x0, x1, l0x, l1x = [t.numpy() for t in axis_coords(W)]
+    l0y, l1y = l0y.astype(np.float64)[:, None], l1y.astype(np.float64)[:, None]
+    l0x, l1x = l0x.astype(np.float64), l1x.astype(np.float64)
+    v = x.astype(np.float64)
+    ra, rb = np.take(v, y0, axis=-2), np.take(v, y1, axis=-2)
+    ha = lerp2_32(l0x, np.take(ra, x0, axis=-1), l1x, np.take(ra, x1, axis=-1))
+    hb = lerp2_32(l0x, np.take(rb, x0, axis=-1), l1x, np.take(rb, x1, axis=-1))
+    return lerp2_32(l0y, ha, l1y, hb).astype(np.float32)
+
+
 # ---- flat Adam --------------------------------------------------------------------------------------------------------------------------
 
 def f32(x):
